@@ -7,7 +7,13 @@ lattice pixels -> sampling / VM interpolation / MLP / compositing -> edge-weight
 -> backward to the VM factors, basis, MLP and se(3) -> Adam steps (scene + pose) -> LR schedule.
 Inputs (images, cameras, parameters) are resident in HBM before the timed region.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config bat_blender_VM] [--stage 4]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config bat_blender_VM] [--stage 4] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, higher_is_better, dtype,
+ms_per_step, ...).  Everything else it can measure -- the in-step roofline with its kernel probe and counter passes, the
+stock-torch GPU baseline, the CPU baseline, the secondary workloads (`extra`), the GPU clocks, and on N > 1 the
+collectives-off leg and the all-reduce timings -- runs with --full only; the --no-* options switch single legs of it off.
+--dump-outputs DIR writes what the last timed step computed (DIR/<name>.npy, see dump_outputs and replay_for_dump).
 
 N = 1 (default): BASELINE.json configs[1], the bat_blender_VM final-stage training step (about 2 000 rays per iteration).
 N > 1: one rank per GPU over RCCL.  Under a launcher (torch.distributed.run: RANK / WORLD_SIZE / MASTER_* in the
@@ -31,6 +37,43 @@ sys.path.insert(0, ROOT)
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
+
+DUMP_SAMPLE = 1 << 19          # --dump-outputs: elements kept of a larger tensor (a fixed, seeded sample)
+DUMP_BUDGET = 64 * 1024 * 1024  # --dump-outputs: bytes of all files together
+
+
+def dump_outputs(path, model, last):
+    """--dump-outputs: what the last timed step handed its caller, one DIR/<name>.npy per array -- `rgb` (the rendered
+    colours of the step's rays), `loss_<term>` (the loss terms and their weighted sum `loss_all`), and `param_<name>`
+    (every tensor of the scene's state dict and the se(3) pose refinements, as the step's optimizer updates left them).
+    float64 stays float64, everything else is written as float32.  A tensor of more than DUMP_SAMPLE elements is
+    represented by the same DUMP_SAMPLE flat indices in every run (numpy generator seeded with 0, sorted)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = []
+    var, loss = last.get("var"), last.get("loss")
+    if var is not None and torch.is_tensor(var.get("rgb")):
+        arrays.append(("rgb", var.rgb))
+    for k, v in (loss or {}).items():
+        if v is not None:
+            arrays.append(("loss_" + k, v if torch.is_tensor(v) else torch.tensor(float(v))))
+    params = list(model.graph.nerf.tensorf.state_dict().items())
+    params.append(("se3_refine.weight", model.graph.se3_refine.weight))
+    for k, v in params:
+        arrays.append(("param_" + k.replace(".", "_"), v))
+    total = 0
+    with torch.no_grad():
+        for name, t in arrays:
+            t = t.detach()
+            flat = t.reshape(-1)
+            if flat.numel() > DUMP_SAMPLE:
+                idx = np.sort(np.random.default_rng(0).choice(flat.numel(), DUMP_SAMPLE, replace=False))
+                flat = flat[torch.from_numpy(idx).to(flat.device)]
+                t = flat
+            a = t.cpu().numpy().astype(np.float64 if t.dtype == torch.float64 else np.float32)
+            total += a.nbytes
+            if total > DUMP_BUDGET:
+                raise RuntimeError("--dump-outputs: more than %d bytes at %s" % (DUMP_BUDGET, name))
+            np.save(os.path.join(path, name + ".npy"), a)
 
 
 def parse():
@@ -56,6 +99,15 @@ def parse():
                          "field (blobs + smooth textured appearance, synthetic.make_gt_scene resampled onto the model's grid) "
                          "and is supervised with images rendered from it at the ground-truth cameras -- the sharp last stage "
                          "of a run that has converged")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline as well: in-step roofline (+ kernel probe, live counter "
+                         "passes), stock-torch GPU baseline, secondary workloads, CPU baseline, GPU clocks; N > 1: the "
+                         "collectives-off leg and the all-reduce timings.  The --no-* options below act on --full runs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed to DIR/<name>.npy (float32 / float64): "
+                         "rendered colours, loss terms, and the parameters as its optimizer steps left them (a fixed seeded "
+                         "sample of every tensor above %d elements).  The same in every run: see replay_for_dump" % DUMP_SAMPLE)
+    ap.add_argument("--dump-replay", metavar="DIR", default=None, help=argparse.SUPPRESS)   # (replay_for_dump's child)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--probe-only", action="store_true",
@@ -437,8 +489,8 @@ def live_pmc_traffic(steps=6, warmup=2):
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import pmc_traffic_instep as PT
     tmp = tempfile.mkdtemp(prefix="jt_pmc_", dir="/tmp")
-    child = [sys.executable, os.path.abspath(__file__), "--steps", str(steps), "--warmup", str(warmup), "--no-cpu-baseline",
-             "--no-probe", "--no-torch-baseline", "--no-extras", "--no-live-pmc"]
+    child = [sys.executable, os.path.abspath(__file__), "--steps", str(steps), "--warmup", str(warmup), "--full",
+             "--no-cpu-baseline", "--no-probe", "--no-torch-baseline", "--no-extras", "--no-live-pmc"]
     env = dict(os.environ, TMPDIR="/tmp", JT_TIME_WALK="1")
     csvs = {}
     line = None
@@ -469,7 +521,7 @@ def live_pmc_traffic(steps=6, warmup=2):
 
 def pmc_traffic_instep(roof, hidden=None, live=None):
     """HBM-side bytes per launch of k_shade_bwd from rocprofv3 --pmc passes over THIS command (separate FETCH_SIZE / WRITE_SIZE
-    runs of `bench.py --no-cpu-baseline --no-probe --no-torch-baseline --no-extras`; FETCH_SIZE doubled as
+    runs of `bench.py --full --no-cpu-baseline --no-probe --no-torch-baseline --no-extras`; FETCH_SIZE doubled as
     MI355X_MICROARCH.md prescribes for gfx950), per shaded sample, scaled by the samples of the live launches.  `live`: the
     record of live_pmc_traffic() -- collected in this very run; otherwise the committed passes (tools/profile_cmd.sh ->
     tools/pmc_traffic_instep.py) are quoted and the source says so; null when neither exists."""
@@ -617,8 +669,8 @@ def run_extras(steps=20, warmup=5):
     shaded-sample counts per iteration -- so that a variant, the default as a child (`default_headline_child`) and the parent's
     own timed loop can be compared to the per cent (the children used to run 10 steps on another lattice)."""
     import subprocess
-    base = [sys.executable, os.path.abspath(__file__), "--steps", "10", "--warmup", "3", "--no-cpu-baseline", "--no-probe",
-            "--no-torch-baseline", "--no-extras"]
+    base = [sys.executable, os.path.abspath(__file__), "--steps", "10", "--warmup", "3", "--full", "--no-cpu-baseline",
+            "--no-probe", "--no-torch-baseline", "--no-extras"]
     same = ["--steps", str(steps), "--warmup", str(warmup)]   # argparse: the later occurrence wins
     cases = [("stage0_blurred", ["--stage", "0"], {}),
              ("stage0_blurred_hipgraph", ["--stage", "0"], {"JT_GRAPH": "1"}),
@@ -712,8 +764,34 @@ def run_extras(steps=20, warmup=5):
     return out
 
 
+def replay_for_dump(path):
+    """--dump-outputs: the float atomics of the timed path sum in a different order every run, and the optimizer turns that
+    round-off of near-zero gradients into whole learning-rate steps, so after a few dozen steps two runs hold different
+    parameters.  The dump therefore comes from a fresh child process of this command (same arguments, same seeds, same host
+    draws: the same iterations) whose steps in front of the last timed one run with order-independent sums
+    (jt_set_deterministic): its last timed step starts from the same state in every run and goes through the timed path's
+    own kernels, so what it returns agrees from run to run to round-off.  The timed steps of this process are not touched."""
+    import subprocess
+    argv, skip = [], False
+    for a in sys.argv[1:]:
+        if skip:
+            skip = False
+        elif a == "--dump-outputs":
+            skip = True
+        elif not (a.startswith("--dump-outputs=") or a == "--full"):
+            argv.append(a)
+    r = subprocess.run([sys.executable, os.path.abspath(__file__)] + argv + ["--dump-replay", path], stdout=subprocess.DEVNULL,
+                       timeout=900)
+    if r.returncode != 0:
+        raise RuntimeError("--dump-outputs: the replay exited with %d" % r.returncode)
+
+
 def main():
     args = parse()
+    if (args.dump_outputs or args.dump_replay) and (args.gpus > 1 or FORCE_DIST):
+        print("bench.py: --dump-outputs needs one process (its replay sums in a fixed order, which the data-parallel path "
+              "does not)", file=sys.stderr)
+        sys.exit(2)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and not FORCE_DIST:
         sys.exit(launch_ranks(args))   # nothing in this process has touched the GPU
     world, rank, local, backend = setup_dist(args)
@@ -722,7 +800,11 @@ def main():
         sys.exit(3)
     dev = "cuda:%d" % local
     import joint_tensorf_amd  # noqa: F401  (fails loudly without the HIP library)
+    from joint_tensorf_amd._lib import lib as jt_lib
     from joint_tensorf_amd.options import make_options
+    # replay_for_dump's child: every step but the last timed one with order-independent sums (unless JT_DETERMINISTIC=1
+    # asked for them everywhere)
+    keep_det = jt_lib.jt_set_deterministic(1) == 1 if args.dump_replay else None
     from joint_tensorf_amd.synthetic import make_views
 
     torch.manual_seed(0)
@@ -788,17 +870,21 @@ def main():
     tape_groups_used = [1]
 
     from joint_tensorf_amd import ops as jops_b
+    last = {}   # --dump-outputs: what the last timed step returned (references only, taken on that step alone)
 
-    def one_step():
+    def one_step(keep=False):
         nonlocal rays_total
         from joint_tensorf_amd.options import Opt
         var = Opt(dict(var_all))
         g = model.graph
         if stepper is not None:
-            stepper.train_iteration(opt, var, force_eager=not use_graph[0])
+            # (replay_for_dump's last step: eager -- the graphs of its child were captured with the fixed-order sums)
+            loss = stepper.train_iteration(opt, var, force_eager=not use_graph[0] or bool(args.dump_replay and keep))
             model.after_iteration(opt)
             rgb = stepper.last_var.rgb
             rays_total += rgb.shape[0] * rgb.shape[1]
+            if keep:
+                last.update(var=stepper.last_var, loss=loss)
             return
         g.it = model.it
         model.optim.zero_grad()
@@ -840,6 +926,8 @@ def main():
         nerf.set_progress(model.it / opt.max_iter)
         model.after_iteration(opt)
         rays_total += n_step
+        if keep:
+            last.update(var=var, loss=loss)
 
     def barrier():
         if world > 1 or FORCE_DIST:
@@ -860,7 +948,8 @@ def main():
         finally:
             np.random.randint = orig_randint
 
-    if not args.no_roofline and stepper is None:
+    roofline = args.full and not args.no_roofline
+    if roofline and stepper is None:
         from joint_tensorf_amd import ops as _jops
         # HIP events around every k_shade_fwd<train> / k_shade_bwd launch; the ones of the timed steps make the roofline
         _jops.STEP_TIMERS = []
@@ -898,12 +987,15 @@ def main():
         rays_total = 0
     n_untimed = len(jops_t.STEP_TIMERS) if jops_t.STEP_TIMERS is not None else 0
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        one_step()
+    for i in range(args.steps):
+        if args.dump_replay and i == args.steps - 1 and not keep_det:
+            jt_lib.jt_set_deterministic(0)   # the last step on the timed path's own kernels
+        one_step(keep=i == args.steps - 1)
     barrier()
     dt = time.perf_counter() - t0
     rays_timed = rays_total
-    clocks = gpu_clocks() if rank == 0 else None   # right behind the timed loop: the chip is still in its working state
+    # right behind the timed loop: the chip is still in its working state
+    clocks = gpu_clocks() if rank == 0 and args.full else None
     all_timers, jops_t.STEP_TIMERS = jops_t.STEP_TIMERS, None
     timers = all_timers[n_untimed:] if all_timers is not None else None
     # JT_BENCH_CHECKSUM=1 (validation of the N > 1 sharding paths against each other): the parameters as the TIMED steps left
@@ -925,10 +1017,16 @@ def main():
                 dist.all_gather(every, mine)
                 param_checksum["identical_on_every_rank"] = bool(all(torch.equal(e, every[0]) for e in every))
                 param_checksum["ranks_compared"] = len(every)
+    if args.dump_replay:
+        dump_outputs(args.dump_replay, model, last)
+        return
+    last.clear()
+    if args.dump_outputs:
+        replay_for_dump(args.dump_outputs)
     # how much of the gradient exchange the backward hid: the same K steps once more with every collective switched off
     # (after the timed region and the checksum; the ranks' parameters drift apart from here on, nothing below reads them)
     dt_nocoll = None
-    if world > 1 or FORCE_DIST:
+    if (world > 1 or FORCE_DIST) and args.full:
         jops_t._DP["no_collectives"] = True
         one_step()
         barrier()
@@ -941,7 +1039,7 @@ def main():
     # the gradient exchange alone: the three collectives of a backward (appearance factors, density factors, basis +
     # MLP; ops.RenderRays.backward) on buffers of the same sizes, not overlapped with anything, median of 5
     allreduce_ms = None
-    if (world > 1 or FORCE_DIST) and jops_t._DP.get("span_elems"):
+    if (world > 1 or FORCE_DIST) and args.full and jops_t._DP.get("span_elems"):
         import torch.distributed as dist
         allreduce_ms = {}
         for (lo, hi), n in sorted(jops_t._DP["span_elems"].items()):
@@ -1022,7 +1120,8 @@ def main():
                                  if world > 1 else "1 GPU")),
             },
         }
-        out["gpu_clocks_after_timed_loop"] = clocks
+        if args.full:
+            out["gpu_clocks_after_timed_loop"] = clocks
         if world > 1 or FORCE_DIST:
             import torch.distributed as dist
             out["ranks"] = {"world_size": dist.get_world_size(), "backend": backend,
@@ -1051,7 +1150,7 @@ def main():
                 tf = model.graph.nerf.tensorf
                 out["grad_checksum_first_step"] = grad_sums[0] if grad_sums else None
                 out["param_checksum"] = param_checksum
-        if not args.no_roofline:
+        if roofline:
             try:
                 from joint_tensorf_amd.options import Opt
                 tf_ = model.graph.nerf.tensorf
@@ -1092,7 +1191,7 @@ def main():
                     out["roofline"]["probe"] = measure_roofline(model, opt, Opt(dict(var_all)))
             except Exception as e:  # keep the bench line even if the timing is unavailable
                 out["roofline"] = {"error": repr(e)}
-        if world == 1 and not strong and not args.no_torch_baseline and args.config == "bat_blender_VM" \
+        if args.full and world == 1 and not strong and not args.no_torch_baseline and args.config == "bat_blender_VM" \
                 and args.scene == "random" and not model.graph.resolve_blur(opt, "vis")[2]:
             try:
                 from joint_tensorf_amd.options import Opt
@@ -1103,7 +1202,7 @@ def main():
                                            "(torch_gpu_baseline)")
             except Exception as e:
                 out["torch_gpu_baseline"] = {"error": repr(e)[:300]}
-        if world == 1 and not strong and not args.no_extras:
+        if args.full and world == 1 and not strong and not args.no_extras:
             # free this process' device memory first: the children build their own models
             del model
             jops_t._WS.clear()
@@ -1111,7 +1210,7 @@ def main():
             out["extra"] = run_extras(args.steps, args.warmup)
         # the CPU baseline LAST: its sweep ends on every logical CPU of the host, and the intra-op pool it leaves behind kept
         # the host-bound eager child workloads above 10-15 % slower when it ran in front of them
-        if world == 1 and not strong and not args.no_cpu_baseline:
+        if args.full and world == 1 and not strong and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(res, S)
         print(json.dumps(out))
     if world > 1 or FORCE_DIST:

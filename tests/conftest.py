@@ -6,6 +6,11 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+# MKL's default GEMM kernels differ by CPU (AVX-512 code paths on Intel processors only), and the CPU oracle's test-time pose
+# optimisation turns that last-bit difference into 1e-3 of its loss trace.  The golden fixtures were captured in MKL's
+# processor-independent mode (tools/make_golden.py, tools/make_engine_trace.py) and the oracle runs in it here, before the
+# first MKL call of the process.
+os.environ["MKL_CBWR"] = "COMPATIBLE"
 
 
 def pytest_configure(config):

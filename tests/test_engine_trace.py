@@ -335,7 +335,14 @@ def _run_on_gpu(name):
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["blender", "llff"])
 def test_engine_on_gpu_follows_the_reference_loop(name):
-    arr, meta, ref_rows, losses, se3, model = _run_on_gpu(name)
+    # in JT_DETERMINISTIC mode (order-independent sums) every run of the same code lands on the same numbers: with the float
+    # atomics the LLFF pose deviation below moved from 1.5e-6 to 1.1e-5 between runs, across its bound
+    from joint_tensorf_amd._lib import lib
+    prev = lib.jt_set_deterministic(1)
+    try:
+        arr, meta, ref_rows, losses, se3, model = _run_on_gpu(name)
+    finally:
+        lib.jt_set_deterministic(prev)
     ref_se3 = arr["trace.se3_after"]
     # How far the two runs can be compared loss by loss is a property of the REFERENCE's loop, measured on the reference itself
     # (tools/round6/loop_sensitivity.py, profiles/round6_llff_loop_sensitivity.txt): the LLFF loop turns a 1e-7 perturbation of
@@ -364,7 +371,8 @@ def test_engine_on_gpu_follows_the_reference_loop(name):
     # different interpolation kernels, optimizer rebuilds, the pose reset).  Measured on MI355X: Blender 9.5e-7 / 1.7e-7 / 9.5e-8
     # (render / L1 / se3) over 48 iterations, LLFF 2.7e-6 over its first 19; the bounds are ~20 x that
     # (LLFF: 2.2e-5 / 5.2e-5 / 1.5e-6 in another run -- the order of the float atomics differs from run to run, and iteration 8,
-    #  the first one behind an upsampling, is already a small amplifier: profiles/round6_llff_loop_sensitivity.txt)
+    #  the first one behind an upsampling, is already a small amplifier: profiles/round6_llff_loop_sensitivity.txt).  In the
+    # JT_DETERMINISTIC mode this test runs in: Blender 1.05e-6 / 2.6e-7 / 1.0e-7, LLFF 5.2e-5 / 7.0e-5 / 7.0e-6, in every run.
     tol = dict(blender=(5e-5, 1e-5, 5e-6), llff=(2e-4, 2e-4, 1e-5))[name]
     assert worst["render"] <= tol[0] and worst["all"] <= tol[0] and worst["L1"] <= tol[1] and worst["se3"] <= tol[2], worst
     assert all(np.isfinite(v) for row in losses for v in row.values())

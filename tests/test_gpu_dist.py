@@ -3,8 +3,8 @@ rendezvous, both on GPU 0), Model.enable_data_parallel -> the renderer's backwar
 three collectives, pose gradients through Model.reduce_pose_gradients.  Checked per sharding mode: (1) the reduced
 gradient of the first step equals the single-process gradient -- "pixel" / "view": of THE iteration one process renders
 (same draws, all views, whole lattice: the ranks' shards partition it); "offset": of the union of the two ranks' own
-lattices; (2) after three optimizer steps both ranks hold identical parameters.  Last: `bench.py --gpus 2` with no
-launcher around it starts its own two ranks."""
+lattices; (2) after three optimizer steps both ranks hold identical parameters.  Last: the bench lines -- a plain
+one-GPU run with its dumped outputs, and `bench.py --gpus 2` with no launcher around it, which starts its own two ranks."""
 import json
 import os
 import socket
@@ -96,6 +96,43 @@ def test_two_ranks_equal_one_process(tmp_path, mode):
           % (mode, worst[1], worst[0], r0["first"]["rays"], r1["first"]["rays"]))
 
 
+def test_bench_plain_line_and_dumped_outputs_repeat(tmp_path):
+    """A plain `bench.py --gpus 1` run: the contract fields of the line, nothing of --full, and --dump-outputs from two runs
+    with the same arguments: equal to the bit under JT_DETERMINISTIC (order-independent sums everywhere), and equal to
+    round-off on the timed path's own float-atomic kernels, after enough steps that two runs' parameters would have drifted
+    apart (the dumped step starts from a reproducible state: bench.replay_for_dump)."""
+    env0 = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "JT_BENCH_SINGLE_DEVICE", "JT_FORCE_DIST",
+              "JT_GRAPH", "JT_DETERMINISTIC"):
+        env0.pop(k, None)
+    for mode in ("deterministic", "default"):
+        env = dict(env0, JT_DETERMINISTIC="1") if mode == "deterministic" else env0
+        lines = []
+        for d in ("a", "b"):
+            r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--stage", "0", "--steps", "20",
+                                "--warmup", "5", "--dump-outputs", str(tmp_path / mode / d)], env=env, capture_output=True,
+                               text=True, timeout=600)
+            assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+            lines.append(json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]))
+        line = lines[0]
+        assert line["unit"] == "rays/s" and line["higher_is_better"] is True and line["dtype"] == "f32" and line["steps"] == 20
+        assert line["value"] > 0 and abs(line["value"] * line["ms_per_step"] * 1e-3 - line["config"]["rays_per_iter_per_gpu"]) \
+            < 1e-6 * line["config"]["rays_per_iter_per_gpu"]
+        assert not {"roofline", "extra", "cpu_baseline", "torch_gpu_baseline", "gpu_clocks_after_timed_loop"} & set(line)
+        a_dir, b_dir = tmp_path / mode / "a", tmp_path / mode / "b"
+        names = sorted(p.name for p in a_dir.iterdir())
+        assert "rgb.npy" in names and "loss_all.npy" in names and any(n.startswith("param_app_plane") for n in names), names
+        assert sum((a_dir / n).stat().st_size for n in names) <= 64 * 1024 * 1024
+        for n in names:
+            a, b = np.load(str(a_dir / n)), np.load(str(b_dir / n))
+            assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), (mode, n)
+            if mode == "deterministic":
+                np.testing.assert_array_equal(a, b, err_msg=n)
+            else:   # round-off of one step's float atomics, against the tensor's largest value
+                err = float(np.abs(a.astype(np.float64) - b).max()) if a.size else 0.0
+                assert err <= 1e-4 * max(float(np.abs(b).max()), 1e-30), (n, err, float(np.abs(b).max()))
+
+
 def test_bench_gpus2_starts_its_own_ranks():
     """`python bench.py --gpus 2` with NO launcher: the script spawns two fresh ranks before touching the GPU (here both
     on GPU 0 over gloo -- the one-GPU functional form), shards ONE iteration over them and prints n_gpus = 2."""
@@ -103,7 +140,8 @@ def test_bench_gpus2_starts_its_own_ranks():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--stage", "0", "--total-rays", "8192",
-                        "--steps", "3", "--warmup", "1", "--no-probe"], env=env, capture_output=True, text=True, timeout=900)
+                        "--steps", "3", "--warmup", "1", "--full", "--no-probe"],
+                       env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["scaling"] == "strong"
@@ -134,7 +172,7 @@ def test_bench_gpus8_single_device(shard):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1",
-                        "--shard", shard, "--no-probe", "--no-cpu-baseline", "--no-torch-baseline", "--no-extras"],
+                        "--shard", shard, "--full", "--no-probe", "--no-cpu-baseline", "--no-torch-baseline", "--no-extras"],
                        env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -173,7 +211,7 @@ def test_rccl_process_group_of_one_rank():
                JT_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("JT_DIST_BACKEND", None)
     env.pop("JT_BENCH_SINGLE_DEVICE", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--full",
                         "--no-probe", "--no-cpu-baseline", "--no-torch-baseline", "--no-extras", "--no-live-pmc"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]

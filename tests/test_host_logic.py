@@ -175,6 +175,34 @@ def test_bench_gpus_n_without_n_gpus_refuses():
     assert r.returncode == 2 and "--gpus 8" in r.stderr and not r.stdout.strip()
 
 
+def test_bench_dump_outputs_writes_float_arrays_with_a_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: one float32 / float64 .npy per array the last timed step returned, a tensor above
+    DUMP_SAMPLE elements as the same seeded sample of its flat indices in every run."""
+    from types import SimpleNamespace
+    import bench
+    from joint_tensorf_amd.options import Opt
+    g = torch.Generator().manual_seed(0)
+    tf = torch.nn.Module()
+    tf.big = torch.nn.Parameter(torch.randn(bench.DUMP_SAMPLE + 1000, generator=g))
+    tf.small = torch.nn.Parameter(torch.randn(3, 4, generator=g, dtype=torch.float64))
+    tf.register_buffer("mask", torch.ones(2, 2, dtype=torch.bool))
+    model = SimpleNamespace(graph=SimpleNamespace(nerf=SimpleNamespace(tensorf=tf),
+                                                  se3_refine=torch.nn.Embedding(5, 6)))
+    last = dict(var=Opt(rgb=torch.rand(2, 7, 3, generator=g)), loss=Opt(render=torch.tensor(0.5), all=torch.tensor(0.75)))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), model, last)
+    a = {p.name: np.load(str(p)) for p in (tmp_path / "a").iterdir()}
+    assert sorted(a) == ["loss_all.npy", "loss_render.npy", "param_big.npy", "param_mask.npy", "param_se3_refine_weight.npy",
+                         "param_small.npy", "rgb.npy"]
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert a["param_small.npy"].dtype == np.float64 and a["param_small.npy"].shape == (3, 4)
+    assert a["rgb.npy"].shape == (2, 7, 3) and float(a["loss_all.npy"]) == 0.75
+    big = a["param_big.npy"]
+    assert big.shape == (bench.DUMP_SAMPLE,) and np.isin(big, tf.big.detach().numpy()).all()
+    for name, v in a.items():
+        np.testing.assert_array_equal(v, np.load(str(tmp_path / "b" / name)))
+
+
 def test_flat_gradient_buffer_zeroes_only_what_nobody_overwrites():
     """ops._zeros_flat carves the gradient tensors of a backward out of one buffer; groups the regularisers' backward is
     about to overwrite completely (RenderRays.backward: density factors, appearance planes under TV) are left unfilled, every

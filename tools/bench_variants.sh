@@ -3,6 +3,7 @@
 # variant "default" = the in-tree libjt_render.so; others = joint_tensorf_amd/lib/variants/<name>.so (tools/build_variant.py)
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 TAG=$1; VARS=$2; shift; shift
+set -- --full "$@"   # the summary below reads the line's roofline block: a --full field
 export JT_TIME_WALK=1
 for v in $VARS; do
   if [ "$v" = default ]; then unset JT_LIB_PATH; else export JT_LIB_PATH=$R/joint_tensorf_amd/lib/variants/$v.so; fi

@@ -18,6 +18,9 @@ Data only: tensors and numbers.  Re-run:  python tools/make_engine_trace.py [--o
 import argparse
 import json
 import os
+
+# MKL in its processor-independent mode (the same GEMM results on every x86-64 CPU): tests/conftest.py runs the oracle so
+os.environ["MKL_CBWR"] = "COMPATIBLE"
 import sys
 import types
 

@@ -15,6 +15,9 @@ import os
 import sys
 import types
 
+# MKL in its processor-independent mode (the same GEMM results on every x86-64 CPU): tests/conftest.py runs the oracle so
+os.environ["MKL_CBWR"] = "COMPATIBLE"
+
 import numpy as np
 import torch
 
@@ -765,7 +768,9 @@ def main():
     with torch.no_grad():
         for p in graph.nerf.tensorf.density_plane:
             p.mul_(22.0 / 40.0)
-    eval_case(bat, camera, opt, graph, var, os.path.join(outdir, "blender_test_optim.npz"))
+    # (the CPU oracle's evaluation tests read this capture; the GPU evaluation tests read blender_test_optim.npz, the capture of
+    #  an earlier run with MKL's default AVX-512 kernels, whose box-face sample decisions the HIP path reproduces at iteration 0)
+    eval_case(bat, camera, opt, graph, var, os.path.join(outdir, "blender_test_optim_mklcnr.npz"))
     # N3: 2-D blur cache of the GT images + edge masks (host torch ops in the reference, every 500 iterations)
     gt_blur_case(bat, opt, os.path.join(outdir, "gt_blur_edge.npz"))
     # N4: alpha-mask volume, masked render, AABB shrink (last: it changes the scene's box and grid)

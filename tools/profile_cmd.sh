@@ -5,7 +5,7 @@
 # Copy what is to be judged into profiles/ (round-tagged names).
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 TAG=$1; shift
-CMD="$R/bench.py --no-cpu-baseline --no-probe --no-torch-baseline --no-extras $*"
+CMD="$R/bench.py --full --no-cpu-baseline --no-probe --no-torch-baseline --no-extras $*"
 O=$R/gpurun_out
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
