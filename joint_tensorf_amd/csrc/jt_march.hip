@@ -439,6 +439,9 @@ __global__ __launch_bounds__(256) void k_march_bwd_scan(Dev D, const float* __re
       s_G[i] = Gw;
     }
   }
+  // lane 0's s_carry writes are read by every lane in pass B: the LDS writes complete before the wave goes on
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_wave_barrier();
   // ---- pass B (reverse) ----
   float suffix = 0.f;  // sum_{j>i} G_j w_j carried from later chunks
   float gnorm = 0.f;   // NDC: dL/d|d|

@@ -1,0 +1,348 @@
+"""Pinned fp64 reference for a hand-built BAT_VMSplit scene and hand-made rays, and the element-wise gradient criterion
+of tests/test_gpu_scatter_shapes.py.
+
+The HIP side runs one forward + backward with fixed random cotangents on rgb and opacity and reads back what its kernels
+decided (the shading mask from last_render_cfg.shade_lists, the ReLU sign words from the record workspace).  The
+reference side runs the oracle in float64 (on the CPU), on the HIP path's ray values, with those decisions pinned
+(app_mask_override / relu_masks_override) and with the scene constants held as their fp32 values (as
+fullsize_util.oracle_cfg does).  The sample geometry is pinned as well: the z values, the in-box test, the sample
+positions, their normalised coordinates and the tap cells and fractions are the fp32 values the product path computes
+(the same separately rounded operations, jt_common.h), taken as exact numbers, and everything after them is fp64.  The
+derivatives with respect to the rays are those of the fp64 expressions (straight-through), so a sample within rounding
+of a texel node takes the same cell -- the same slope -- on both sides.  Without that pinning an fp32 tap weight that
+rounds to 0 (a sample on a node or on a box face) meets an fp64 weight of 1e-8, and the bilinear slope on either side of
+a node differs by O(1).
+
+Per factor (plane or line) it also returns, besides the fp64 gradient T:
+  * M, the magnitude: the sum over contributions of |tap weight x upstream gradient|.  The map from a factor to its
+    samples (_sample_plane / _sample_line) is linear with non-negative weights, so with U the fp64 gradient that reaches
+    the samples, autograd.grad(samples, factor, grad_outputs=|U|) is M, and M >= |T| element by element;
+  * F, the footprint: the same call with grad_outputs = ones, > 0.
+A factor gradient G of an fp32 implementation is then judged element by element (factor_errors): G == 0 exactly
+outside F (anything else is a stray write), |G - T| <= kappa 2^-24 M inside."""
+import copy
+
+import torch
+
+from oracle import tensorf_oracle as O  # checker only
+
+EPS32 = 2.0 ** -24
+GROUPS = ("density_plane", "density_line", "app_plane", "app_line")
+FACTORS = ["%s.%d" % (g, i) for g in GROUPS for i in range(3)]
+DENSE = ["basis_mat.weight", "mlp.w1", "mlp.b1", "mlp.w2", "mlp.b2", "mlp.w3", "mlp.b3"]
+# scene kinds of the two configurations: (appearance channels, app_dim, hidden units, shading, activation, shift)
+KINDS = {"blender": (48, 27, 64, "MLP_Fea", "softplus", -10.0), "llff": (20, 20, 32, "MLP_Fea_WeakView", "relu", 0.0)}
+UNIT = 1.0 / 128  # texel pitch of every axis of a thin scene (exact in fp32: sample positions on the faces are exact)
+
+
+def thin_box(grid):
+    """aabb of a scene whose three axes have the same texel pitch UNIT (stepSize = UNIT * step_ratio, exactly), centred"""
+    h = [(g - 1) * UNIT / 2 for g in grid]
+    return [-h[0], -h[1], -h[2], h[0], h[1], h[2]]
+
+
+def scene_cfg(aabb, grid, near_far, kind, step_ratio, thres, device, dtype=torch.float32):
+    """the oracle's SceneCfg of a scene of `kind`; with dtype = float64 the fp32 VALUES of the constants"""
+    _, _, _, mode, act, shift = KINDS[kind]
+    cfg = O.SceneCfg(aabb, grid, near_far, step_ratio=step_ratio, density_shift=shift, distance_scale=25.0,
+                     fea2denseAct=act, rayMarch_weight_thres=thres, shadingMode=mode, view_pe=2, fea_pe=2).to(device)
+    for k in ("aabb", "aabbSize", "invaabbSize", "units", "stepSize"):
+        setattr(cfg, k, getattr(cfg, k).to(dtype))
+    return cfg
+
+
+def build_scene(kind, grid, aabb, dev, cd=16, near_far=(0.5, 40.0), step_ratio=0.5, thres=1e-7, depth=1.5, seed=0):
+    """A BAT_VMSplit of the given kind with positive density factors whose field has about `depth` optical depth over
+    the longest axis (so that the transmittance stays away from zero along it and every texel of the long line is in
+    the footprint), random appearance factors and MLP."""
+    import joint_tensorf_amd as jt
+    ca, app_dim, hid, mode, act, shift = KINDS[kind]
+    torch.manual_seed(seed)
+    tf = jt.BAT_VMSplit(aabb, grid, dev, density_n_comp=[cd] * 3, appearance_n_comp=[ca] * 3, app_dim=app_dim,
+                        near_far=list(near_far), shadingMode=mode, density_shift=shift, distance_scale=25.0, view_pe=2,
+                        fea_pe=2, featureC=hid, step_ratio=step_ratio, fea2denseAct=act, rayMarch_weight_thres=thres,
+                        volume_init_scale=0.1, volume_init_bias=0.0)
+    extent = max(aabb[3 + a] - aabb[a] for a in range(3))
+    sigma = depth / (25.0 * extent)
+    feat = sigma if act == "relu" else 10.0 + float(torch.log(torch.expm1(torch.tensor(sigma, dtype=torch.float64))))
+    a = (feat / (3 * cd)) ** 0.5  # feat = sum over 3 planes x cd channels of plane x line, both ~ a
+    g = torch.Generator().manual_seed(seed + 1)
+    with torch.no_grad():
+        for p in list(tf.density_plane) + list(tf.density_line):
+            p.copy_((a * (0.5 + torch.rand(p.shape, generator=g))).to(p.device))
+    return tf
+
+
+def ray_set(aabb, n_axial, n_oblique, n_graze, axis=2, seed=0, dist=3.0, n_miss=0):
+    """hand-made rays [R, 3] (fp32, CPU) for a scene box:
+      * a bundle along `axis` entering through the end face (origin exactly 1 before the face, direction the unit axis:
+        the unjittered first sample sits exactly on the face, the samples step UNIT * step_ratio along the line);
+      * oblique rays at random points of the box from random directions;
+      * grazing rays through the neighbourhood of the box's long edges, across the long axis;
+      * rays that miss the box (they count towards the batch's size, which the walk's shape depends on)."""
+    g = torch.Generator().manual_seed(seed)
+    lo, hi = torch.tensor(aabb[:3]), torch.tensor(aabb[3:])
+    size = hi - lo
+    os_, ds_ = [], []
+    if n_axial:
+        # cross-section positions off the texel nodes (a quarter texel in from a random cell corner)
+        o = lo + size * torch.rand(n_axial, 3, generator=g)
+        o = torch.floor((o - lo) / UNIT) * UNIT + lo + UNIT * (0.25 + 0.5 * torch.rand(n_axial, 3, generator=g))
+        o = torch.minimum(o, hi - UNIT / 4)
+        o[:, axis] = lo[axis] - 1.0
+        d = torch.zeros(n_axial, 3)
+        d[:, axis] = 1.0
+        os_.append(o), ds_.append(d)
+    if n_oblique:
+        tgt = lo + size * torch.rand(n_oblique, 3, generator=g)
+        d = torch.randn(n_oblique, 3, generator=g)
+        d = d / d.norm(dim=-1, keepdim=True)
+        os_.append(tgt - dist * d), ds_.append(d)
+    if n_graze:
+        tgt = lo + size * torch.rand(n_graze, 3, generator=g)
+        side = [a for a in range(3) if a != axis]
+        for a in side:  # onto one of the four long edges, a small random distance in or out
+            pick = torch.rand(n_graze, generator=g) < 0.5
+            tgt[:, a] = torch.where(pick, lo[a], hi[a]) + 0.3 * UNIT * torch.randn(n_graze, generator=g)
+        d = torch.randn(n_graze, 3, generator=g)
+        d[:, axis] = 0.1 * d[:, axis]
+        d = d / d.norm(dim=-1, keepdim=True)
+        os_.append(tgt - dist * d), ds_.append(d)
+    if n_miss:
+        tgt = lo + size * torch.rand(n_miss, 3, generator=g)
+        d = torch.randn(n_miss, 3, generator=g)
+        d = d / d.norm(dim=-1, keepdim=True)
+        os_.append(tgt + (dist + size.norm()) * d), ds_.append(d)  # outside, looking away
+    return torch.cat(os_).float().contiguous(), torch.cat(ds_).float().contiguous()
+
+
+def cotangents(R, seed):
+    g = torch.Generator().manual_seed(seed)
+    return torch.randn(R, 3, generator=g, dtype=torch.float64), torch.randn(R, generator=g, dtype=torch.float64)
+
+
+def _device_kernel_names(prof):
+    names = set()
+    for e in prof.events():
+        if e.device_type == torch.autograd.DeviceType.CUDA:
+            names.add(e.name)
+    return names
+
+
+def run_hip(tf, o, d, S, ndc=False, white=True, cot_seed=0, profile=False):
+    """One forward + backward of tf through the HIP path (eval sampling: no jitter).  Returns the outputs, the 20
+    parameter gradients, the ray gradients, the decisions the kernels took and (profile=True) the names of the device
+    kernels that ran."""
+    from tests.fullsize_util import read_relu_masks
+    dev = tf.density_plane[0].device
+    for p in tf.parameters():
+        p.grad = None
+    og, dg = o.to(dev).requires_grad_(True), d.to(dev).requires_grad_(True)
+    R = o.shape[0]
+    cr, co = cotangents(R, cot_seed)
+
+    def step():
+        out = tf(None, og, dg, white_bg=white, is_train=False, ndc_ray=ndc, N_samples=S)
+        ((out[0] * cr.to(dev).float()).sum() + (out[2] * co.to(dev).float()).sum()).backward()
+        torch.cuda.synchronize()
+        return out
+
+    kernels, attempts = None, 0
+    if profile:
+        from torch.profiler import ProfilerActivity, profile as tprofile
+        # (the profiler has been seen to return a trace without this library's backward kernels once in ~40 rows on
+        #  MI355X: the same deterministic step is then recorded once more, from zeroed gradients; the caller reports it)
+        for attempts in range(1, 3):
+            for p in tf.parameters():
+                p.grad = None
+            og.grad = dg.grad = None
+            with tprofile(activities=[ProfilerActivity.CUDA]) as prof:
+                out = step()
+            kernels = _device_kernel_names(prof)
+            if any("k_march_bwd_scan" in n for n in kernels):   # every backward launches the scan
+                break
+    else:
+        out = step()
+    grads = {}
+    for grp in GROUPS:
+        for i in range(3):
+            grads["%s.%d" % (grp, i)] = getattr(tf, grp)[i].grad.detach().clone()
+    grads["basis_mat.weight"] = tf.basis_mat.weight.grad.detach().clone()
+    for k, t in zip(("w1", "b1", "w2", "b2", "w3", "b3"), tf.renderModule.weights()):
+        grads["mlp." + k] = t.grad.detach().clone()
+    offset, sidx = tf.last_render_cfg.shade_lists
+    cnt = (offset[1:] - offset[:-1]).long()
+    sel = torch.arange(S, device=dev)[None] < cnt[:, None]
+    mask = torch.zeros(R, S, dtype=torch.bool, device=dev)
+    mask[sel.nonzero()[:, 0], (sidx.to(torch.int32) & 0xFFFF).long()[sel]] = True
+    n = int(offset[-1])
+    assert int(mask.sum()) == n
+    relu = read_relu_masks(tf, n) if n else None
+    return dict(rgb=out[0].detach(), depth=out[1].detach(), opacity=out[2].detach(), grads=grads,
+                g_o=og.grad.detach() if og.grad is not None else torch.zeros_like(og),
+                g_d=dg.grad.detach() if dg.grad is not None else torch.zeros_like(dg),
+                shade_mask=mask, relu=relu, kernels=kernels, profile_attempts=attempts)
+
+
+def _cfg32(cfg):
+    c = copy.copy(cfg)
+    for k in ("aabb", "aabbSize", "invaabbSize", "units", "stepSize"):
+        setattr(c, k, getattr(cfg, k).float())
+    return c
+
+
+def _pinned_samplers(decide_dev):
+    """sample_ray / sample_ray_ndc that take the z values, the in-box decision and the positions in fp32 on
+    `decide_dev` (as the product path does); the positions are returned in the rays' type with the fp32 values and the
+    derivatives of o + d z"""
+    plain, ndc = O.sample_ray, O.sample_ray_ndc
+
+    def wrap(fn):
+        def f(cfg, rays_o, rays_d, N_samples, jitter=None):
+            dev = decide_dev or rays_o.device
+            c32 = _cfg32(cfg).to(dev)
+            p32, z32, valid = fn(c32, rays_o.detach().float().to(dev), rays_d.detach().float().to(dev), N_samples,
+                                 None if jitter is None else jitter.float().to(dev))
+            z, valid = z32.to(rays_o.device).to(rays_o.dtype), valid.to(rays_o.device)
+            pts = rays_o[..., None, :] + rays_d[..., None, :] * z[..., None]
+            pts = p32.to(rays_o.device).to(rays_o.dtype) + (pts - pts.detach())
+            return pts, z, valid
+        return f
+    return wrap(plain), wrap(ndc)
+
+
+def _pinned_normalize(cfg, xyz):
+    """normalize_coord with the fp32 value of (xyz - aabb[0]) * invaabbSize - 1 (three separately rounded fp32
+    operations, jt_common.h normalize) and the derivative of the expression in xyz's type"""
+    n = (xyz - cfg.aabb[0]) * cfg.invaabbSize - 1
+    n32 = (xyz.detach().float() - cfg.aabb[0].float()) * cfg.invaabbSize.float() - 1
+    return n32.to(n.dtype) + (n - n.detach())
+
+
+def _axis32(g, size):
+    """floor cell and fraction of the normalised coordinates g along an axis of `size` texels: the fp32 values of
+    ix = ((g + 1) * 0.5) * (size - 1) (jt_common.h axis_taps; g holds fp32 values), the derivative of the fp64 ix"""
+    ix32 = ((g.detach().float() + 1.0) * 0.5) * float(size - 1)
+    fl = torch.floor(ix32)
+    ix = (g + 1) * 0.5 * (size - 1)
+    return fl.long(), (ix32 - fl).to(g.dtype) + (ix - ix.detach())
+
+
+def pinned_taps(plane, gx, gy):
+    """bilinear_taps with the cells and fractions of the product path's fp32 arithmetic (_axis32); plane [1, C, H, W]
+    at normalised (gx, gy) [P] -> [C, P]"""
+    _, C, H, W = plane.shape
+    x0, fx = _axis32(gx, W)
+    y0, fy = _axis32(gy, H)
+    out = 0
+    p = plane[0]
+    for dy, wy in ((0, 1 - fy), (1, fy)):
+        for dx, wx in ((0, 1 - fx), (1, fx)):
+            xx, yy = x0 + dx, y0 + dy
+            ok = (xx >= 0) & (xx < W) & (yy >= 0) & (yy < H)
+            v = p[:, yy.clamp(0, H - 1), xx.clamp(0, W - 1)]
+            out = out + v * (wx * wy * ok)[None]
+    return out
+
+
+def _pinned_plane(plane, gx, gy, use_taps=False):
+    return pinned_taps(plane, gx, gy)
+
+
+def _pinned_line(line, g, use_taps=False):
+    return pinned_taps(line, torch.zeros_like(g), g)
+
+
+def reference(cfg, params, o, d, S, cot, ndc=False, white=True, app_mask=None, relu=None, keep=False, decide_dev=None):
+    """The oracle in params' dtype on params' device for rays (o, d) with the discrete decisions pinned; returns outputs,
+    gradients of every parameter (T), the ray gradients and per factor M and F (see the module docstring).  keep=True
+    also returns the recorded samples: (factor name, factor, samples [C, P], U [C, P]) per sampling call."""
+    dev, dt = params["density_plane"][0].device, params["density_plane"][0].dtype
+    names = {id(v): n for n, v in O.flat_params(params)}
+    rec = []
+    saved = (O._sample_plane, O._sample_line, O.sample_ray, O.sample_ray_ndc, O.normalize_coord)
+
+    def wrap(fn):
+        def f(factor, *a):
+            out = fn(factor, *a)
+            if id(factor) in names and out.requires_grad:
+                out.retain_grad()
+                rec.append((names[id(factor)], factor, out))
+            return out
+        return f
+    oc, dc = o.to(dev).to(dt).requires_grad_(True), d.to(dev).to(dt).requires_grad_(True)
+    O._sample_plane, O._sample_line = wrap(_pinned_plane), wrap(_pinned_line)
+    O.sample_ray, O.sample_ray_ndc = _pinned_samplers(decide_dev)
+    O.normalize_coord = _pinned_normalize
+    rep = {}
+    try:
+        rgb, depth, acc = O.render(cfg, params, oc, dc, S, white_bg=white, ndc_ray=ndc, app_mask_override=app_mask,
+                                   relu_masks_override=relu, relu_report=rep)
+    finally:
+        O._sample_plane, O._sample_line, O.sample_ray, O.sample_ray_ndc, O.normalize_coord = saved
+    tot = (rgb * cot[0].to(dev).to(dt)).sum() + (acc * cot[1].to(dev).to(dt)).sum()
+    if tot.requires_grad:
+        tot.backward(retain_graph=True)
+    T = {n: (torch.zeros_like(v) if v.grad is None else v.grad.detach().clone()) for n, v in O.flat_params(params)}
+    M = {n: torch.zeros_like(T[n]) for n in FACTORS}
+    F = {n: torch.zeros_like(T[n]) for n in FACTORS}
+    kept = []
+    for n, factor, out in rec:
+        U = out.grad if out.grad is not None else torch.zeros_like(out)
+        M[n] += torch.autograd.grad(out, factor, grad_outputs=U.abs(), retain_graph=True)[0]
+        F[n] += torch.autograd.grad(out, factor, grad_outputs=torch.ones_like(out), retain_graph=True)[0]
+        if keep:
+            kept.append((n, factor, out, U))
+    del rec
+    return dict(samples=kept, rgb=rgb.detach(), depth=depth.detach(), opacity=acc.detach(), T=T, M=M,
+                F={n: v > 0 for n, v in F.items()},
+                g_o=torch.zeros_like(oc) if oc.grad is None else oc.grad.detach(),
+                g_d=torch.zeros_like(dc) if dc.grad is None else dc.grad.detach(), relu=rep)
+
+
+def params_of(tf, dtype=torch.float64):
+    sd = {k: v.detach().clone().contiguous().to(dtype) for k, v in tf.state_dict().items()}
+    p = O.params_from_state_dict(sd, prefix="")
+    for _, v in O.flat_params(p):
+        v.requires_grad_(True)
+    return p
+
+
+def run_reference(tf, kind, hip, o, d, S, cot_seed=0, ndc=False, white=True, step_ratio=0.5, thres=1e-7):
+    """the fp64 reference of run_hip's iteration, pinned to its shading mask and ReLU signs.  It runs on the CPU (the
+    same fp64 arithmetic; the GPU's fp64 atomics in grid_sample's backward made the long-line rows ten times slower),
+    with the fp32 sample decisions taken on the GPU like the product path's."""
+    cfg = scene_cfg(tf.aabb.view(-1).tolist(), tf.gridSize.tolist(), [float(tf.near_far[0]), float(tf.near_far[1])], kind,
+                    step_ratio, thres, "cpu", torch.float64)
+    relu = None if hip["relu"] is None else [m.cpu() for m in hip["relu"]]
+    params = params_of(tf)
+    for _, v in O.flat_params(params):
+        v.data = v.data.cpu()
+    return reference(cfg, params, o.cpu(), d.cpu(), S, cotangents(o.shape[0], cot_seed), ndc=ndc, white=white,
+                     app_mask=hip["shade_mask"].cpu(), relu=relu, decide_dev=tf.density_plane[0].device)
+
+
+def factor_errors(G, T, M, F):
+    """(number of writes outside F, worst |G - T| / (2^-24 M) inside F, its index).  An element of F with M == 0 takes
+    ratio 0 when G == T and inf otherwise."""
+    G, T, M = G.double(), T.double(), M.double()
+    stray = int(((G != 0) & ~F).sum())
+    diff = (G - T).abs()
+    ratio = torch.where(M > 0, diff / (EPS32 * M).clamp_min(1e-300), torch.where(diff > 0, float("inf"), 0.0))
+    ratio = torch.where(F, ratio, torch.zeros_like(ratio))
+    k = int(ratio.flatten().argmax())
+    return stray, float(ratio.flatten()[k]), k
+
+
+def ray_atol(g, t, rtol):
+    """the smallest atol (relative to max |t|) with |g - t| <= rtol |t| + atol max |t| element by element"""
+    g, t = g.double(), t.double()
+    scale = float(t.abs().max())
+    if scale == 0.0:
+        return 0.0 if float(g.abs().max()) == 0.0 else float("inf")
+    return max(0.0, float(((g - t).abs() - rtol * t.abs()).max()) / scale)
+
+
+def max_rel(g, t):
+    g, t = g.double(), t.double()
+    return float((g - t).abs().max() / t.abs().max().clamp_min(1e-30))

@@ -1,0 +1,146 @@
+"""The element-wise gradient criterion of tests/test_gpu_scatter_shapes.py checked on the oracle alone (CPU, fp64): the
+magnitude M bounds the reference gradient, the reference gradient is zero outside the footprint F, and a single lost or
+misplaced sample contribution -- the failure of branch-specific scatter code -- is caught element by element, at the
+kappa the GPU module enforces, where the norm-wise check of test_gpu_fuzz.py (3e-3 of the tensor's largest element) lets
+it pass; on a scene with a long line, most single contributions are caught (the rest are below kappa 2^-24 of their
+texel)."""
+import torch
+
+from oracle import tensorf_oracle as O
+from tests import pinned_ref as P
+from tests.test_gpu_scatter_shapes import KAPPA as KAPPA_GPU
+
+KAPPA = max(KAPPA_GPU.values())   # the largest kappa tests/test_gpu_scatter_shapes.py holds the kernels to
+FUZZ_TOL = 3e-3         # test_gpu_fuzz.py: max |G - T| <= 3e-3 max |T|
+
+
+def _scene(seed=0, grid=(6, 5, 11), rays=(6, 12, 4)):
+    grid = list(grid)
+    aabb = P.thin_box(grid)
+    cd, ca, app_dim, hid = 4, 6, 5, 16
+    g = torch.Generator().manual_seed(seed)
+    dt = torch.float64
+    sigma = 1.5 / (25.0 * (grid[2] - 1) * P.UNIT)
+    a = ((10.0 + float(torch.log(torch.expm1(torch.tensor(sigma, dtype=dt))))) / (3 * cd)) ** 0.5
+    p = dict(density_plane=[], density_line=[], app_plane=[], app_line=[])
+    for i in range(3):
+        m0, m1 = O.MAT_MODE[i]
+        v = O.VEC_MODE[i]
+        p["density_plane"].append(a * (0.5 + torch.rand(1, cd, grid[m1], grid[m0], generator=g, dtype=dt)))
+        p["density_line"].append(a * (0.5 + torch.rand(1, cd, grid[v], 1, generator=g, dtype=dt)))
+        p["app_plane"].append(0.3 * torch.randn(1, ca, grid[m1], grid[m0], generator=g, dtype=dt))
+        p["app_line"].append(0.3 * torch.randn(1, ca, grid[v], 1, generator=g, dtype=dt))
+    p["basis"] = 0.3 * torch.randn(app_dim, 3 * ca, generator=g, dtype=dt)
+    n_in = app_dim + 3 + 2 * 2 * app_dim + 2 * 2 * 3  # MLP_Fea: [f, d, PE(f), PE(d)] with fea_pe = view_pe = 2
+    p["mlp"] = dict(w1=0.3 * torch.randn(hid, n_in, generator=g, dtype=dt), b1=0.1 * torch.randn(hid, generator=g, dtype=dt),
+                    w2=0.3 * torch.randn(hid, hid, generator=g, dtype=dt), b2=0.1 * torch.randn(hid, generator=g, dtype=dt),
+                    w3=0.3 * torch.randn(3, hid, generator=g, dtype=dt), b3=0.1 * torch.randn(3, generator=g, dtype=dt))
+    for _, v in O.flat_params(p):
+        v.requires_grad_(True)
+    cfg = P.scene_cfg(aabb, grid, [0.5, 40.0], "blender", 0.5, 1e-7, "cpu", dt)
+    o, d = P.ray_set(aabb, *rays, seed=seed)
+    S = 2 * grid[2] + 6
+    ref = P.reference(cfg, p, o, d, S, P.cotangents(o.shape[0], seed), keep=True)
+    return grid, ref
+
+
+def _fuzz_passes(G, T):
+    return float((G - T).abs().max()) <= FUZZ_TOL * float(T.abs().max()) + 1e-10
+
+
+def test_magnitude_bounds_gradient_and_footprint_holds_it():
+    grid, ref = _scene()
+    for n in P.FACTORS:
+        T, M, F = ref["T"][n], ref["M"][n], ref["F"][n]
+        assert (T.abs() <= M * (1 + 1e-12)).all(), n
+        assert (M[~F] == 0).all() and (T[~F] == 0).all(), n
+        assert F.any(), n
+        # the exact gradient passes its own criterion with kappa 0, and writes nothing outside F
+        assert P.factor_errors(T, T, M, F)[:2] == (0, 0.0), n
+    # the bundle along the long axis enters through the end face: every texel of the long line is in the footprint
+    assert ref["F"]["density_line.0"].all() and ref["F"]["app_line.0"].all()
+    assert ref["T"]["density_line.0"].shape[2] == grid[2]
+
+
+def _one_contribution(ref, name):
+    """one sample's contribution c to one texel of factor `name` with |c| below the norm-wise tolerance and above the
+    element-wise bound at twice KAPPA: (texel index, neighbour index along the line, c)"""
+    T, M = ref["T"][name], ref["M"][name]
+    tmax = float(T.abs().max())
+    for n, factor, out, U in ref["samples"]:
+        if n != name:
+            continue
+        for p in range(out.shape[1]):
+            if not bool((U[:, p] != 0).any()):
+                continue
+            gout = torch.zeros_like(out)
+            gout[:, p] = U[:, p]
+            c = torch.autograd.grad(out, factor, grad_outputs=gout, retain_graph=True)[0].flatten()
+            ok = (c.abs() > 0) & (c.abs() <= 0.9 * FUZZ_TOL * tmax) & (c.abs() > 2 * KAPPA * P.EPS32 * M.flatten())
+            if ok.any():
+                k = int(ok.nonzero()[0])
+                nb = k + 1 if (k + 1) % T.shape[2] != 0 else k - 1   # the next texel along the line, same channel
+                return k, nb, float(c[k])
+    raise AssertionError("no small contribution found for %s" % name)
+
+
+def test_lost_or_moved_contribution_is_caught_elementwise_only():
+    _, ref = _scene()
+    for name in ("density_line.0", "app_line.0"):
+        T, M, F = ref["T"][name], ref["M"][name], ref["F"][name]
+        k, nb, c = _one_contribution(ref, name)
+        lost = T.clone().flatten()
+        lost[k] -= c
+        lost = lost.view_as(T)
+        moved = lost.clone().flatten()
+        moved[nb] += c
+        moved = moved.view_as(T)
+        for G in (lost, moved):
+            assert _fuzz_passes(G, T), name   # the norm-wise check does not see it
+            stray, ratio, _ = P.factor_errors(G, T, M, F)
+            assert stray > 0 or ratio > KAPPA, (name, ratio)
+        # the texel that lost it fails on its own
+        assert P.factor_errors(lost, T, M, F)[1] > 2 * KAPPA * 0.99
+
+
+def test_stray_write_outside_footprint_is_caught():
+    _, ref = _scene()
+    hit = False
+    for name in P.FACTORS:
+        T, M, F = ref["T"][name], ref["M"][name], ref["F"][name]
+        if F.all():
+            continue
+        G = T.clone()
+        G[~F] = 1e-30 * float(T.abs().max() + 1)
+        assert _fuzz_passes(G, T)
+        assert P.factor_errors(G, T, M, F)[0] == int((~F).sum())
+        hit = True
+    assert hit, "every factor's footprint is complete: no stray write to test"
+
+
+def test_single_contributions_of_a_long_line_are_caught():
+    """every single-sample contribution of a random subset, removed on its own, on a scene whose long line has 160
+    texels and whose texels each sum the contributions of many samples: the element-wise check, at the kappa of the
+    factor's family, catches most of them.  The ones it misses are below kappa 2^-24 of their texel's magnitude: samples
+    whose upstream gradient is orders of magnitude below the texel's other samples' (deep in a ray, grazing)."""
+    _, ref = _scene(seed=1, grid=(12, 9, 160), rays=(16, 24, 8))
+    g = torch.Generator().manual_seed(3)
+    for name in ("density_line.0", "app_line.0", "density_plane.1", "app_plane.1"):
+        M = ref["M"][name].flatten()
+        kappa = KAPPA_GPU[name.split(".")[0]]
+        caught = total = 0
+        for n, factor, out, U in ref["samples"]:
+            if n != name:
+                continue
+            live = (U != 0).any(0).nonzero()[:, 0]
+            for p in live[torch.randperm(live.numel(), generator=g)[:40]].tolist():
+                gout = torch.zeros_like(out)
+                gout[:, p] = U[:, p]
+                c = torch.autograd.grad(out, factor, grad_outputs=gout, retain_graph=True)[0].flatten()
+                for k in (c != 0).nonzero()[:, 0].tolist():
+                    total += 1
+                    caught += int(abs(float(c[k])) > kappa * P.EPS32 * float(M[k]))
+        print("\n[checker] %s: %d of %d single contributions caught at kappa %g" % (name, caught, total, kappa))
+        assert total >= 100, (name, total)
+        # (measured: 82 %, 86 %, 87 % and 88 %; the misses are contributions below kappa 2^-24 of their texel)
+        assert caught >= (0.4 if name.startswith("app_plane") else 0.75) * total, (name, caught, total)
