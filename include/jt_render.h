@@ -38,9 +38,9 @@ extern "C" {
  * jt_reg_losses_fused, removed jt_pose_fused* and redefined matrix-mode bit 2 at version 1100; 1200 = round 6: those changes,
  * jt_shade_lean_tape / jt_shade_set_lean_tape, the workspace no longer carries the tile lists unless that variant is selected;
  * 1201: + jt_chip_geometry; 1202: + jt_shade_workspace_layout; 1203: + jt_march_forward_pose / jt_march_backward_pose; 1204: +
- * jt_lattice_indices.  Additions bump the last two digits, anything a caller built against the old header would get wrong bumps the
+ * jt_lattice_indices; 1205: + jt_ssim_forward / jt_ssim_workspace_bytes.  Additions bump the last two digits, anything a caller built against the old header would get wrong bumps the
  * hundreds). */
-#define JT_VERSION 1204
+#define JT_VERSION 1205
 
 #define JT_OK 0
 #define JT_ERR_ARG 1         /* null pointer / bad size */
@@ -430,6 +430,20 @@ int jt_finite_check(const JtFiniteItem* items, int n_items, int32_t* status_word
  * sum_h (d[h+1][w] - d[h][w])^2 / grid_h + sum_w (d[h][w+1] - d[h][w])^2 / grid_w for depth [n_views][grid_h][grid_w].  The BAT
  * yamls weight the term 0.0 and only log it; a non-zero weight goes through the host mirror's differentiable ops. */
 int jt_tv_depth_forward(const float* depth, int n_views, int grid_h, int grid_w, float* out, void* stream);
+
+/* SSIM of n_views image pairs, the `pytorch_ssim.ssim(rgb_map, var.image)` of the evaluation loop (model/nerf.py:550; as stock
+ * ops: five grouped conv2d calls and ~20 element-wise launches per image, in fp32).  pred, target: [n_views][n_channels][height]
+ * [width] fp32.  Window: the outer product of g[k] = exp(-(k - 5)^2 / (2 * 1.5^2)), k = 0..10, normalised to sum 1 and rounded
+ * to fp32.  Per channel, with ZERO padding of 5 (the window is not renormalised at the border): mu1 = g*x, mu2 = g*y, s1 =
+ * g*(x x) - mu1^2, s2 = g*(y y) - mu2^2, s12 = g*(x y) - mu1 mu2, ssim_map = (2 mu1 mu2 + C1)(2 s12 + C2) / ((mu1^2 + mu2^2 + C1)
+ * (s1 + s2 + C2)), C1 = 0.01^2, C2 = 0.03^2.  ssim[v] (fp64) = mean of view v's map over channels and pixels; ssim_map (fp32,
+ * same shape as the inputs) may be NULL.  The moments, the formula and the sums are fp64; the per-view sum has ONE order (no
+ * atomics): the same bits run to run, with JT_DETERMINISTIC on or off.  Any height, width >= 1.  workspace:
+ * jt_ssim_workspace_bytes(...) bytes, caller-provided, 8-byte aligned, overwritten.  JT_ERR_UNSUPPORTED when n_views *
+ * n_channels * height * width reaches 2^31 (or n_views * n_channels exceeds 65 535). */
+int jt_ssim_forward(const float* pred, const float* target, int n_views, int n_channels, int height, int width, double* ssim,
+                    float* ssim_map, void* workspace, size_t workspace_bytes, void* stream);
+size_t jt_ssim_workspace_bytes(int n_views, int n_channels, int height, int width);
 
 /* The weighted sum of Model.summarize_loss (model/tensorf.py:31-47) over the photometric term and the three
  * regularisers, one launch each way:  total = w_render render[0] + w_l1 reg3[0] + w_tv_density reg3[1] +

@@ -1,0 +1,91 @@
+"""The files an evaluation leaves behind (model/bat.py:255-259, model/nerf.py:530-556,568-572,619-627): quant_pose.txt, quant.txt
+and the PNGs of the rendered views.  Host code on host tensors: nothing here needs a GPU.
+
+quant.txt keeps the reference's four columns `i psnr ssim lpips`; LPIPS needs trained AlexNet weights that this build does not
+carry, so the column holds `nan`."""
+import os
+import shutil
+import subprocess
+
+import torch
+
+_PIL_WARNED = []
+
+
+def to_uint8(img):
+    """[C, H, W] float in any range -> [H, W, C] uint8: clamp to [0, 1], then torchvision's to_pil_image conversion of float
+    tensors (x * 255 truncated to a byte).  The clamp is this build's: the reference does not clamp and wraps around on an
+    inverse depth above 1."""
+    x = torch.nan_to_num(img.detach().to("cpu", torch.float32), nan=0.0).clamp(0.0, 1.0)   # (0 / 0 of an empty ray: black)
+    return x.mul(255).to(torch.uint8).permute(1, 2, 0).contiguous()
+
+
+def _pil():
+    try:
+        from PIL import Image
+        return Image
+    except Exception as e:   # no pictures without it; the numbers are still written
+        if not _PIL_WARNED:
+            _PIL_WARNED.append(True)
+            print("joint_tensorf_amd: PIL cannot be imported (%s): the evaluation PNGs are skipped" % (e,))
+        return None
+
+
+def save_png(img, path):
+    """[3, H, W] -> RGB, [1, H, W] -> L (8-bit grey), converted by to_uint8.  Returns False when PIL is missing."""
+    Image = _pil()
+    if Image is None:
+        return False
+    a = to_uint8(img).numpy()
+    if a.shape[2] == 1:
+        Image.fromarray(a[:, :, 0]).save(path)
+    elif a.shape[2] == 3:
+        Image.fromarray(a).save(path)
+    else:
+        raise ValueError("save_png: 1 or 3 channels, got %d" % a.shape[2])
+    return True
+
+
+def write_quant_pose(output_path, R_error, t_error):
+    """quant_pose.txt: `i err_R err_t` per training view (model/bat.py:255-259)"""
+    with open(os.path.join(output_path, "quant_pose.txt"), "w") as f:
+        for i, (r, t) in enumerate(zip(R_error, t_error)):
+            f.write("{} {} {}\n".format(i, float(r), float(t)))
+
+
+def write_quant(output_path, psnr_per_view, ssim_per_view):
+    """quant.txt: `i psnr ssim lpips` per held-out view (model/nerf.py:568-572), lpips = nan"""
+    with open(os.path.join(output_path, "quant.txt"), "w") as f:
+        for i, (p, s) in enumerate(zip(psnr_per_view, ssim_per_view)):
+            f.write("{} {} {} {}\n".format(i, float(p), float(s), float("nan")))
+
+
+def write_view_pngs(directory, i, rgb=None, rgb_GT=None, depth=None):
+    """<directory>/rgb_<i>.png, rgb_GT_<i>.png, depth_<i>.png (model/nerf.py:554-556, 619-620); maps are [C, H, W]"""
+    os.makedirs(directory, exist_ok=True)
+    ok = True
+    for name, img in (("rgb", rgb), ("rgb_GT", rgb_GT), ("depth", depth)):
+        if img is not None:
+            ok = save_png(img, os.path.join(directory, "{}_{}.png".format(name, i))) and ok
+    return ok
+
+
+def normalized_invdepth(opt, invdepth_map):
+    """model/nerf.py:544-548: NDC inverse depths are mapped from [0.05, far - near] to [0, 1], others are kept"""
+    if opt.camera.ndc:
+        min_r, max_r = 0.05, opt.nerf.depth.range[1] - opt.nerf.depth.range[0]
+        return (invdepth_map - min_r) / (max_r - min_r)
+    return invdepth_map
+
+
+def encode_videos(output_path, frame_dir, it=None):
+    """The reference's two ffmpeg commands (model/nerf.py:623-627), run only when an ffmpeg executable is on PATH."""
+    exe = shutil.which("ffmpeg")
+    if exe is None:
+        print("joint_tensorf_amd: no ffmpeg on PATH: the frames stay in %s, no video is encoded" % frame_dir)
+        return False
+    for kind in ("rgb", "depth"):
+        out = "{}/novel_view_{}_{}.webm".format(output_path, kind, it)
+        subprocess.run([exe, "-y", "-framerate", "30", "-i", "{}/{}_%d.png".format(frame_dir, kind), "-vcodec", "libvpx-vp9",
+                        "-pix_fmt", "yuv420p", out], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, check=False)
+    return True

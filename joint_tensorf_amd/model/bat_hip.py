@@ -1015,10 +1015,54 @@ class Model(torch.nn.Module):
                                                      "fixed-point sum in the pose or factor gradients)")) if bits & b]
             raise FloatingPointError("non-finite values since the last check in: %s (iteration %d)" % ("; ".join(what), self.it))
 
+    @torch.no_grad()
+    def novel_view_poses(self, opt):
+        """The camera path of generate_videos_synthesis (model/nerf.py:580-598), [N, 3, 4] on opt.device: a turn round the scene box
+        (Blender / t2, N = 120) or a small oscillation about the centre-most optimised camera (N = 60), both scaled by sim3.s1 /
+        sim3.s0 of the training cameras' Procrustes alignment.  opt.eval_novel_views overrides N."""
+        from .. import novel_views
+        pose_pred, pose_GT = self.get_all_training_poses(opt)
+        joint = opt.model in ("barf", "bat", "bat_hip")
+        poses = pose_pred if joint else pose_GT
+        blender = opt.data.dataset in ("blender", "t2")
+        scale = 1
+        if joint and (blender or opt.data.dataset == "llff"):
+            _, sim3 = self.prealign_cameras(opt, pose_pred, pose_GT)
+            scale = sim3.s1 / sim3.s0
+        n = int(opt.eval_novel_views) if _has(opt, "eval_novel_views") and opt.eval_novel_views else (120 if blender else 60)
+        if blender:
+            pose_novel = novel_views.around_bbox(opt.data.scene_bbox, n=n, scale=scale)
+        else:
+            idx_center = (poses - poses.mean(dim=0, keepdim=True))[..., 3].norm(dim=-1).argmin()
+            pose_novel = novel_views.around_pose(poses[idx_center], n=n, scale=scale)
+        return pose_novel.to(opt.device)
+
+    @torch.no_grad()
     def generate_videos_synthesis(self, opt, eps=1e-10, it=None):
-        """model/nerf.py:574-640 writes novel-view videos through ffmpeg / wandb: reference engine, out of scope.  Kept
-        as a callable no-op so that the train_3d.py sequence runs through."""
-        print("joint_tensorf_amd: generate_videos_synthesis is not part of this build (evaluate_full renders the test views)")
+        """model/nerf.py:574-627: the novel views of novel_view_poses through the sliced eval render, with the intrinsics of the first
+        test view, written to <output_path>/novel_view/{rgb,depth}_<i>.png and encoded by the reference's two ffmpeg commands when
+        an ffmpeg is installed.  Without an opt.output_path there is nowhere to write: nothing is rendered.  Returns None, as the
+        reference's does (its wandb uploads are not part of this build)."""
+        from .. import eval_io
+        if not (_has(opt, "output_path") and opt.output_path):
+            print("joint_tensorf_amd: generate_videos_synthesis without opt.output_path: nothing to write, nothing rendered")
+            return None
+        g = self.graph
+        g.eval()
+        pose_novel = self.novel_view_poses(opt)
+        novel_path = "{}/novel_view".format(opt.output_path)
+        os.makedirs(novel_path, exist_ok=True)
+        first = Opt(dict(next(iter(self.test_loader))))
+        intr_inv, intr = first.intr_inv[:1].to(opt.device), first.intr[:1].to(opt.device)
+        for i, pose in enumerate(pose_novel):
+            ret = g.render_by_slices(opt, pose[None], intr_inv=intr_inv, intr=intr)
+            # (model/nerf.py:609: in NDC this is depth / opacity, not evaluate_full's plain depth)
+            invdepth = ret.depth / ret.opacity if opt.camera.ndc else 1 / (ret.depth / ret.opacity + eps)
+            rgb_map = ret.rgb.view(-1, opt.H, opt.W, 3).permute(0, 3, 1, 2)
+            invdepth_map = eval_io.normalized_invdepth(opt, invdepth.view(-1, opt.H, opt.W, 1).permute(0, 3, 1, 2))
+            if not eval_io.write_view_pngs(novel_path, i, rgb=rgb_map[0], depth=invdepth_map[0]):
+                return None      # no PIL: no frames, nothing to encode
+        eval_io.encode_videos(opt.output_path, novel_path, it=it)
         return None
 
     # ---- evaluation (SURVEY 8(f) N1) ---------------------------------------------------------------------------
@@ -1222,8 +1266,9 @@ class Model(torch.nn.Module):
 
     @torch.no_grad()
     def evaluate_view(self, opt, var, eps=1e-10):
-        """The per-view body of nerf.Model.evaluate_full (model/nerf.py:534-548): optional test-time pose
-        optimisation, the sliced full-image render and PSNR.  SSIM / LPIPS need packages outside this build."""
+        """The per-view body of nerf.Model.evaluate_full (model/nerf.py:534-551): optional test-time pose
+        optimisation, the sliced full-image render, PSNR, and SSIM on the device (ops.ssim: csrc/jt_metrics.hip)."""
+        from .. import eval_io
         g = self.graph
         g.eval()
         if opt.model in ("barf", "bat", "bat_hip") and opt.optim.test_photo and not var.get("test_optimised", False):
@@ -1233,12 +1278,17 @@ class Model(torch.nn.Module):
         rgb_map = var.rgb.view(-1, opt.H, opt.W, 3).permute(0, 3, 1, 2)
         invdepth_map = invdepth.view(-1, opt.H, opt.W, 1).permute(0, 3, 1, 2)
         psnr = -10 * g.MSE_loss(rgb_map, var.image).log10().item()
-        return Opt(psnr=psnr, rgb_map=rgb_map, invdepth_map=invdepth_map, var=var)
+        ssim = ops.ssim(rgb_map, var.image).mean().item()     # (model/nerf.py:550: one view per batch)
+        return Opt(psnr=psnr, ssim=ssim, rgb_map=rgb_map, invdepth_map=invdepth_map,
+                   invdepth_map_normalized=eval_io.normalized_invdepth(opt, invdepth_map), var=var)
 
     def evaluate_full(self, opt, test_views=None, pose_GT=None, eps=1e-10):
-        """model/bat.py:241-263 + model/nerf.py:525-572: camera alignment errors, then PSNR per held-out view.
+        """model/bat.py:241-263 + model/nerf.py:525-572: camera alignment errors, then PSNR and SSIM per held-out view.
         `test_views`: an iterable of per-view batches (idx, pose, intr, intr_inv, image); default self.test_loader, as
-        in the reference's `evaluate_full(opt)`."""
+        in the reference's `evaluate_full(opt)`.  With an opt.output_path the reference's result files are written:
+        quant_pose.txt and quant.txt (rank 0; the LPIPS column holds nan) and test_view/{rgb,rgb_GT,depth}_<i>.png (every rank
+        its own views)."""
+        from .. import eval_io
         if test_views is None:
             test_views = [{k: (v.to(opt.device) if torch.is_tensor(v) else v) for k, v in dict(b).items()}
                           for b in self.test_loader]
@@ -1250,6 +1300,15 @@ class Model(torch.nn.Module):
         # (no collective on the render path); the per-view PSNRs are gathered at the end
         import torch.distributed as dist
         world, rank = (dist.get_world_size(), dist.get_rank()) if (dist.is_available() and dist.is_initialized()) else (1, 0)
+        out_path = opt.output_path if (_has(opt, "output_path") and opt.output_path) else None
+        if rank == 0:
+            print("--------------------------")
+            print("rot:   {:8.3f}".format(np.rad2deg(float(error.R.mean()))))
+            print("trans: {:10.5f}".format(float(error.t.mean())))
+            print("--------------------------")
+            if out_path:
+                os.makedirs(out_path, exist_ok=True)
+                eval_io.write_quant_pose(out_path, error.R.tolist(), error.t.tolist())
         test_views = list(test_views)
         mine = list(range(rank, len(test_views), world))
         # opt.optim.test_batch = V > 1: the test-time pose optimisation of V views at a time (one iteration serves V views;
@@ -1261,15 +1320,34 @@ class Model(torch.nn.Module):
             for a in range(0, len(mine_views), V):
                 done += self.evaluate_test_time_photometric_optim_batched(opt, mine_views[a:a + V])
             mine_views = done
-        res = [self.evaluate_view(opt, v) for v in mine_views]
+        res = []
+        for i, v in zip(mine, mine_views):
+            r = self.evaluate_view(opt, v)
+            res.append(r)
+            if out_path:
+                eval_io.write_view_pngs("{}/test_view".format(out_path), i, rgb=r.rgb_map[0], rgb_GT=r.var.image[0],
+                                        depth=r.invdepth_map_normalized[0])
         psnr = torch.full((len(test_views),), float("nan"), device=opt.device, dtype=torch.float64)
+        ssim = torch.full((len(test_views),), float("nan"), device=opt.device, dtype=torch.float64)
         for i, r in zip(mine, res):
             psnr[i] = r.psnr
+            ssim[i] = r.ssim
         if world > 1:
             psnr = torch.nan_to_num(psnr, nan=0.0)
             dist.all_reduce(psnr)
-        return Opt(R_error=error.R, t_error=error.t, views=res, psnr_per_view=psnr.tolist(),
-                   psnr=float(psnr.mean()) if len(test_views) else float("nan"))
+            ssim = torch.nan_to_num(ssim, nan=0.0)
+            dist.all_reduce(ssim)
+        out = Opt(R_error=error.R, t_error=error.t, views=res, psnr_per_view=psnr.tolist(),
+                  psnr=float(psnr.mean()) if len(test_views) else float("nan"), ssim_per_view=ssim.tolist(),
+                  ssim=float(ssim.mean()) if len(test_views) else float("nan"))
+        if rank == 0:
+            print("--------------------------")
+            print("PSNR:  {:8.2f}".format(out.psnr))
+            print("SSIM:  {:8.2f}".format(out.ssim))
+            print("--------------------------")
+            if out_path:
+                eval_io.write_quant(out_path, out.psnr_per_view, out.ssim_per_view)
+        return out
 
     # ---- 2-D blur cache of the supervising images + edge masks ----------------------------------
     @torch.no_grad()

@@ -1160,6 +1160,23 @@ def tv_depth_value(depth, n_views, grid_h, grid_w):
     return out[0]
 
 
+def ssim(pred, target, return_map=False):
+    """SSIM of every image pair of a batch, pred / target [V, C, H, W] fp32: the `pytorch_ssim.ssim(rgb_map, var.image)` of the
+    evaluation loop (model/nerf.py:550) per view, as two launches on the current stream (jt_ssim_forward: fp64 moments, formula and
+    sums in one fixed order).  Returns a [V] float64 tensor on the device -- no host read here -- and with `return_map` the
+    per-pixel map [V, C, H, W] fp32 as well.  Value only: the reference has no SSIM loss."""
+    if pred.dim() != 4 or pred.shape != target.shape:
+        raise ValueError("ssim: pred and target must both be [V, C, H, W] (got %s and %s)" % (tuple(pred.shape), tuple(target.shape)))
+    x, y = pred.detach().contiguous().float(), target.detach().contiguous().float()
+    V, C, H, W = x.shape
+    out = torch.empty(V, device=x.device, dtype=torch.float64)
+    smap = torch.empty_like(x) if return_map else None
+    nbytes = lib.jt_ssim_workspace_bytes(V, C, H, W)
+    ws = torch.empty(max(nbytes // 8, 1), device=x.device, dtype=torch.float64)   # (the caching allocator: capturable)
+    check(lib.jt_ssim_forward(ptr(x), ptr(y), V, C, H, W, ptr(out), ptr(smap), ptr(ws), nbytes, _stream()), "jt_ssim_forward")
+    return (out, smap) if return_map else out
+
+
 class LossSumDyn(torch.autograd.Function):
     """LossSum with the four weights read from device memory (`w4`, rewritten by the caller with poke_floats): the
     launch arguments of a captured hipGraph stay the same while the host schedule changes the weights."""

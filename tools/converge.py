@@ -56,6 +56,10 @@ def build(args, device="cuda:0"):
     opt.optim.test_photo = args.test_iter > 0
     opt.train_graph = bool(args.graph)
     opt.freq = dict(scalar=0, val=0, ckpt=0)
+    if getattr(args, "output_path", None):
+        # the reference's result files: model.ckpt, quant_pose.txt, quant.txt, test_view/*.png and, with --novel-views, the frames
+        opt.output_path = args.output_path
+        opt.eval_novel_views = int(getattr(args, "novel_views", 0) or 0)
     torch.manual_seed(args.seed)
     np.random.seed(args.seed)
     model = bat_hip.Model(opt)
@@ -98,6 +102,10 @@ def main():
     ap.add_argument("--test-iter", type=int, default=0, help="test-time pose optimisation iterations per held-out view")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--graph", action="store_true")
+    ap.add_argument("--output-path", default=None, help="write the checkpoint and evaluate_full's result files here")
+    ap.add_argument("--novel-views", type=int, default=0,
+                    help="with --output-path: also render this many novel-view frames (opt.eval_novel_views; the full path "
+                         "has 120 / 60)")
     ap.add_argument("--report-every", type=int, default=0)
     ap.add_argument("--llff-baseline", type=float, default=0.0)
     ap.add_argument("--llff-focus", type=float, default=0.0)
@@ -136,11 +144,14 @@ def main():
     r1, t1 = pose_errors(opt, model)
     rrel = relative_rotation_error(opt, model)
     res = model.evaluate_full(opt)
+    if args.output_path and args.novel_views > 0:
+        model.generate_videos_synthesis(opt)
     print(json.dumps(dict(final=True, iterations=model.it, train_seconds=round(t_train, 2), loss=round(float(loss.all), 6),
                           rot_deg_start=round(r0, 4), rot_deg_end=round(r1, 4), trans_start=round(t0, 5),
                           trans_end=round(t1, 5), rot_gain=round(r0 / max(r1, 1e-9), 1),
                           trans_gain=round(t0 / max(t1, 1e-9), 1), rot_rel_deg_end=round(rrel, 4), test_psnr=round(res.psnr, 2),
-                          psnr_per_view=[round(p, 2) for p in res.psnr_per_view])), flush=True)
+                          psnr_per_view=[round(p, 2) for p in res.psnr_per_view], test_ssim=round(res.ssim, 4),
+                          ssim_per_view=[round(v, 4) for v in res.ssim_per_view])), flush=True)
     st = getattr(model, "train_stepper", None)
     if st is not None:  # which grid stages ran replayed, which eager: (iteration, grid, choice, host ms eager, GPU ms replayed)
         print(json.dumps(dict(launch=st.stats, launch_mode_per_stage=st.decisions)), flush=True)
