@@ -87,7 +87,10 @@ def oracle_cfg(opt, tf, dtype=torch.float32):
 def read_relu_masks(tf, n):
     """The ReLU signs the product path took for its n shaded samples (entry order = ray-major, ascending sample), read
     back from the record workspace the training forward left (layout: jt_shade_record_layout).  Two [n, hidden] bool
-    tensors (layer 1, layer 2)."""
+    tensors (layer 1, layer 2).  The light record set of a pose-only forward (JT_SHADE_POSE_ONLY) is read the same way:
+    it keeps the tile stride and the sign rows of the training tape of the library's current modes (the rows it does not
+    need stay unwritten), so it must be read under the modes the forward ran with -- tests/test_gpu_pose_paths.py pins
+    its reference to these words and would meet ReLU disagreements far from zero if they were another run's."""
     import ctypes
     from joint_tensorf_amd import ops
     from joint_tensorf_amd._lib import lib

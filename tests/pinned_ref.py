@@ -73,13 +73,28 @@ def build_scene(kind, grid, aabb, dev, cd=16, near_far=(0.5, 40.0), step_ratio=0
     return tf
 
 
-def ray_set(aabb, n_axial, n_oblique, n_graze, axis=2, seed=0, dist=3.0, n_miss=0):
+def _off_node(lo, hi, size, n, g):
+    """n positions in the box a quarter to three quarters of a texel in from a random cell corner: off the texel nodes"""
+    o = lo + size * torch.rand(n, 3, generator=g)
+    o = torch.floor((o - lo) / UNIT) * UNIT + lo + UNIT * (0.25 + 0.5 * torch.rand(n, 3, generator=g))
+    return torch.minimum(o, hi - UNIT / 4)
+
+
+def ray_set(aabb, n_axial, n_oblique, n_graze, axis=2, seed=0, dist=3.0, n_miss=0, n_far_side=0, n_far_entry=0):
     """hand-made rays [R, 3] (fp32, CPU) for a scene box:
       * a bundle along `axis` entering through the end face (origin exactly 1 before the face, direction the unit axis:
         the unjittered first sample sits exactly on the face, the samples step UNIT * step_ratio along the line);
       * oblique rays at random points of the box from random directions;
       * grazing rays through the neighbourhood of the box's long edges, across the long axis;
-      * rays that miss the box (they count towards the batch's size, which the walk's shape depends on)."""
+      * rays that miss the box (they count towards the batch's size, which the walk's shape depends on);
+      * far-side rays: a bundle along +`axis` like the first, whose coordinate on one of the two other axes (alternating)
+        is exactly that axis' `hi`: every in-box sample sits on that axis' far node (floor(ix) == size - 1, the sample
+        is in the box because the in-box test is !(p > hi)) -- and, like every full-length ray of the first bundle, the
+        one sample on the far end face sits on the long axis' far node as well;
+      * far-entry rays: along -`axis` from exactly 1 beyond the `hi` end face, cross-section off the nodes: the first
+        sample sits exactly on the far node of `axis`, no other sample of the ray is on a far node.
+    The last two families are appended behind the others and draw from a generator of their own: the rays of a call
+    without them are bit for bit those of earlier versions."""
     g = torch.Generator().manual_seed(seed)
     lo, hi = torch.tensor(aabb[:3]), torch.tensor(aabb[3:])
     size = hi - lo
@@ -113,6 +128,22 @@ def ray_set(aabb, n_axial, n_oblique, n_graze, axis=2, seed=0, dist=3.0, n_miss=
         d = torch.randn(n_miss, 3, generator=g)
         d = d / d.norm(dim=-1, keepdim=True)
         os_.append(tgt + (dist + size.norm()) * d), ds_.append(d)  # outside, looking away
+    gf = torch.Generator().manual_seed(seed + 7919)
+    if n_far_side:
+        o = _off_node(lo, hi, size, n_far_side, gf)
+        side = [a for a in range(3) if a != axis]
+        for k, a in enumerate(side):
+            o[k::2, a] = hi[a]
+        o[:, axis] = lo[axis] - 1.0
+        d = torch.zeros(n_far_side, 3)
+        d[:, axis] = 1.0
+        os_.append(o), ds_.append(d)
+    if n_far_entry:
+        o = _off_node(lo, hi, size, n_far_entry, gf)
+        o[:, axis] = hi[axis] + 1.0
+        d = torch.zeros(n_far_entry, 3)
+        d[:, axis] = -1.0
+        os_.append(o), ds_.append(d)
     return torch.cat(os_).float().contiguous(), torch.cat(ds_).float().contiguous()
 
 
@@ -129,10 +160,68 @@ def _device_kernel_names(prof):
     return names
 
 
-def run_hip(tf, o, d, S, ndc=False, white=True, cot_seed=0, profile=False):
+def run_hip(tf, o, d, S, ndc=False, white=True, cot_seed=0, profile=False, pose_only=False):
     """One forward + backward of tf through the HIP path (eval sampling: no jitter).  Returns the outputs, the 20
     parameter gradients, the ray gradients, the decisions the kernels took and (profile=True) the names of the device
-    kernels that ran."""
+    kernels that ran.  pose_only: no parameter wants a gradient for this step (requires_grad restored afterwards), only
+    the rays do -- the render takes the pose-only kernels; `grads` is None, `param_grads` the number of parameters that
+    received a gradient all the same (0), and the decisions are those of this run's own (pose-only) record set."""
+    if pose_only:
+        params = list(tf.parameters())
+        keep = [p.requires_grad for p in params]
+        for p in params:
+            p.requires_grad_(False)
+        try:
+            return _run_hip(tf, o, d, S, ndc, white, cot_seed, profile, True)
+        finally:
+            for p, k in zip(params, keep):
+                p.requires_grad_(k)
+    return _run_hip(tf, o, d, S, ndc, white, cot_seed, profile, False)
+
+
+GUARD_BYTES, GUARD_FILL = 512, 0xA5
+
+
+class guard_band:
+    """While active, every float32 / int32 / int16 device tensor that torch.empty(n0, n1, ..., device=, dtype=) hands out
+    (the form in which joint_tensorf_amd.ops creates the buffers its kernels write) is a view of an allocation with
+    GUARD_BYTES more behind it, filled with GUARD_FILL; violations() lists the tensors behind which a byte changed.  A
+    kernel that writes up to GUARD_BYTES past its output -- a partial last tile treated as a full one is 31 entries of
+    12 bytes -- is caught, and the stray write lands in memory that belongs to the test."""
+
+    def __init__(self):
+        self.held = []
+
+    def __enter__(self):
+        self.orig = torch.empty
+        held, orig = self.held, self.orig
+
+        def empty(*size, **kw):
+            dt = kw.get("dtype")
+            if (size and all(type(s) is int for s in size) and set(kw) == {"device", "dtype"}
+                    and dt in (torch.float32, torch.int32, torch.int16) and torch.device(kw["device"]).type == "cuda"):
+                n = 1
+                for s in size:
+                    n *= s
+                base = orig(n + GUARD_BYTES // dt.itemsize, **kw)
+                base[n:].view(torch.uint8).fill_(GUARD_FILL)
+                held.append((tuple(size), base, n))
+                return base[:n].view(*size)
+            return orig(*size, **kw)
+        torch.empty = empty
+        return self
+
+    def __exit__(self, *exc):
+        torch.empty = self.orig
+        return False
+
+    def violations(self):
+        return [(shape, int((base[n:].view(torch.uint8) != GUARD_FILL).sum())) for shape, base, n in self.held
+                if bool((base[n:].view(torch.uint8) != GUARD_FILL).any())]
+
+
+def _run_hip(tf, o, d, S, ndc, white, cot_seed, profile, pose_only):
+    import contextlib
     from tests.fullsize_util import read_relu_masks
     dev = tf.density_plane[0].device
     for p in tf.parameters():
@@ -140,11 +229,17 @@ def run_hip(tf, o, d, S, ndc=False, white=True, cot_seed=0, profile=False):
     og, dg = o.to(dev).requires_grad_(True), d.to(dev).requires_grad_(True)
     R = o.shape[0]
     cr, co = cotangents(R, cot_seed)
+    guard = guard_band() if pose_only else None
+    overruns = []
 
     def step():
-        out = tf(None, og, dg, white_bg=white, is_train=False, ndc_ray=ndc, N_samples=S)
-        ((out[0] * cr.to(dev).float()).sum() + (out[2] * co.to(dev).float()).sum()).backward()
-        torch.cuda.synchronize()
+        with (guard if guard is not None else contextlib.nullcontext()):
+            out = tf(None, og, dg, white_bg=white, is_train=False, ndc_ray=ndc, N_samples=S)
+            ((out[0] * cr.to(dev).float()).sum() + (out[2] * co.to(dev).float()).sum()).backward()
+            torch.cuda.synchronize()
+        if guard is not None:
+            overruns.extend(guard.violations())
+            del guard.held[:]
         return out
 
     kernels, attempts = None, 0
@@ -163,13 +258,15 @@ def run_hip(tf, o, d, S, ndc=False, white=True, cot_seed=0, profile=False):
                 break
     else:
         out = step()
-    grads = {}
-    for grp in GROUPS:
-        for i in range(3):
-            grads["%s.%d" % (grp, i)] = getattr(tf, grp)[i].grad.detach().clone()
-    grads["basis_mat.weight"] = tf.basis_mat.weight.grad.detach().clone()
-    for k, t in zip(("w1", "b1", "w2", "b2", "w3", "b3"), tf.renderModule.weights()):
-        grads["mlp." + k] = t.grad.detach().clone()
+    grads, param_grads = None, sum(p.grad is not None for p in tf.parameters())
+    if not pose_only:
+        grads = {}
+        for grp in GROUPS:
+            for i in range(3):
+                grads["%s.%d" % (grp, i)] = getattr(tf, grp)[i].grad.detach().clone()
+        grads["basis_mat.weight"] = tf.basis_mat.weight.grad.detach().clone()
+        for k, t in zip(("w1", "b1", "w2", "b2", "w3", "b3"), tf.renderModule.weights()):
+            grads["mlp." + k] = t.grad.detach().clone()
     offset, sidx = tf.last_render_cfg.shade_lists
     cnt = (offset[1:] - offset[:-1]).long()
     sel = torch.arange(S, device=dev)[None] < cnt[:, None]
@@ -181,7 +278,8 @@ def run_hip(tf, o, d, S, ndc=False, white=True, cot_seed=0, profile=False):
     return dict(rgb=out[0].detach(), depth=out[1].detach(), opacity=out[2].detach(), grads=grads,
                 g_o=og.grad.detach() if og.grad is not None else torch.zeros_like(og),
                 g_d=dg.grad.detach() if dg.grad is not None else torch.zeros_like(dg),
-                shade_mask=mask, relu=relu, kernels=kernels, profile_attempts=attempts)
+                shade_mask=mask, relu=relu, kernels=kernels, profile_attempts=attempts, param_grads=param_grads,
+                overruns=overruns)
 
 
 def _cfg32(cfg):
@@ -253,12 +351,14 @@ def _pinned_line(line, g, use_taps=False):
     return pinned_taps(line, torch.zeros_like(g), g)
 
 
-def reference(cfg, params, o, d, S, cot, ndc=False, white=True, app_mask=None, relu=None, keep=False, decide_dev=None):
+def reference(cfg, params, o, d, S, cot, ndc=False, white=True, app_mask=None, relu=None, keep=False, decide_dev=None,
+              ray_only=False):
     """The oracle in params' dtype on params' device for rays (o, d) with the discrete decisions pinned; returns outputs,
     gradients of every parameter (T), the ray gradients and per factor M and F (see the module docstring).  keep=True
-    also returns the recorded samples: (factor name, factor, samples [C, P], U [C, P]) per sampling call."""
+    also returns the recorded samples: (factor name, factor, samples [C, P], U [C, P]) per sampling call.  ray_only: the
+    outputs and the ray gradients alone (the parameters should then not require a gradient; T, M and F are empty)."""
     dev, dt = params["density_plane"][0].device, params["density_plane"][0].dtype
-    names = {id(v): n for n, v in O.flat_params(params)}
+    names = {} if ray_only else {id(v): n for n, v in O.flat_params(params)}
     rec = []
     saved = (O._sample_plane, O._sample_line, O.sample_ray, O.sample_ray_ndc, O.normalize_coord)
 
@@ -282,7 +382,11 @@ def reference(cfg, params, o, d, S, cot, ndc=False, white=True, app_mask=None, r
         O._sample_plane, O._sample_line, O.sample_ray, O.sample_ray_ndc, O.normalize_coord = saved
     tot = (rgb * cot[0].to(dev).to(dt)).sum() + (acc * cot[1].to(dev).to(dt)).sum()
     if tot.requires_grad:
-        tot.backward(retain_graph=True)
+        tot.backward(retain_graph=not ray_only)
+    if ray_only:
+        return dict(samples=[], rgb=rgb.detach(), depth=depth.detach(), opacity=acc.detach(), T={}, M={}, F={},
+                    g_o=torch.zeros_like(oc) if oc.grad is None else oc.grad.detach(),
+                    g_d=torch.zeros_like(dc) if dc.grad is None else dc.grad.detach(), relu=rep)
     T = {n: (torch.zeros_like(v) if v.grad is None else v.grad.detach().clone()) for n, v in O.flat_params(params)}
     M = {n: torch.zeros_like(T[n]) for n in FACTORS}
     F = {n: torch.zeros_like(T[n]) for n in FACTORS}
@@ -308,18 +412,74 @@ def params_of(tf, dtype=torch.float64):
     return p
 
 
-def run_reference(tf, kind, hip, o, d, S, cot_seed=0, ndc=False, white=True, step_ratio=0.5, thres=1e-7):
+def run_reference(tf, kind, hip, o, d, S, cot_seed=0, ndc=False, white=True, step_ratio=0.5, thres=1e-7, ray_only=False,
+                  slice_entries=1 << 16):
     """the fp64 reference of run_hip's iteration, pinned to its shading mask and ReLU signs.  It runs on the CPU (the
     same fp64 arithmetic; the GPU's fp64 atomics in grid_sample's backward made the long-line rows ten times slower),
-    with the fp32 sample decisions taken on the GPU like the product path's."""
+    with the fp32 sample decisions taken on the GPU like the product path's.  ray_only (a pose-only iteration): outputs
+    and ray gradients alone, the rays taken in slices of about slice_entries shaded samples (rays are independent)."""
     cfg = scene_cfg(tf.aabb.view(-1).tolist(), tf.gridSize.tolist(), [float(tf.near_far[0]), float(tf.near_far[1])], kind,
                     step_ratio, thres, "cpu", torch.float64)
     relu = None if hip["relu"] is None else [m.cpu() for m in hip["relu"]]
     params = params_of(tf)
     for _, v in O.flat_params(params):
         v.data = v.data.cpu()
+    if ray_only:
+        for _, v in O.flat_params(params):
+            v.requires_grad_(False)
+        mask = hip["shade_mask"].cpu()
+        cot = cotangents(o.shape[0], cot_seed)
+        ends = torch.cumsum(mask.sum(1), 0)             # shaded entries up to and including each ray (ray-major order)
+        parts, rep, a = [], {}, 0
+        while a < o.shape[0]:
+            e0 = int(ends[a - 1]) if a else 0
+            b = max(a + 1, int(torch.searchsorted(ends, torch.tensor(e0 + slice_entries), right=True)))
+            b = min(b, o.shape[0])
+            e1 = int(ends[b - 1])
+            r = None if relu is None else [m[e0:e1] for m in relu]
+            part = reference(cfg, params, o[a:b].cpu(), d[a:b].cpu(), S, (cot[0][a:b], cot[1][a:b]), ndc=ndc, white=white,
+                             app_mask=mask[a:b], relu=r, decide_dev=tf.density_plane[0].device, ray_only=True)
+            for k, v in part.pop("relu").items():
+                rep[k] = max(rep.get(k, 0.0), v) if k == "max_abs" else rep.get(k, 0) + v
+            parts.append(part)
+            a = b
+        out = {k: torch.cat([p[k] for p in parts]) for k in ("rgb", "depth", "opacity", "g_o", "g_d")}
+        out["relu"] = rep
+        return out
     return reference(cfg, params, o.cpu(), d.cpu(), S, cotangents(o.shape[0], cot_seed), ndc=ndc, white=white,
                      app_mask=hip["shade_mask"].cpu(), relu=relu, decide_dev=tf.density_plane[0].device)
+
+
+def far_node_samples(aabb, grid, near_far, o, d, S, ndc=False, step_ratio=0.5, device="cpu"):
+    """(valid [R, S], far [R, S, 3]) from the pinned fp32 geometry alone (the oracle's sampler and normalisation in
+    fp32, _axis32's cell): far[r, s, a] says that in-box sample s of ray r sits on the far node of axis a,
+    floor(ix) == size - 1 -- its upper tap is out of range, the case in which the kernels must mask taps (grid_sample's
+    zero padding) instead of interpolating in the nested form."""
+    cfg = scene_cfg(aabb, grid, list(near_far), "llff", step_ratio, 1e-7, device)   # (the kind does not enter the geometry)
+    fn = O.sample_ray_ndc if ndc else O.sample_ray
+    pts, _, valid = fn(cfg, o.float().to(device), d.float().to(device), S)
+    n = O.normalize_coord(cfg, pts)
+    far = torch.stack([_axis32(n[..., a], grid[a])[0] == grid[a] - 1 for a in range(3)], -1) & valid[..., None]
+    return valid.cpu(), far.cpu()
+
+
+def census(far, shade_mask, chunk=1 << 22):
+    """Tile census of a pose-only backward from the reference side: the shaded entries in the kernels' order (ray-major,
+    ascending sample), cut into backward chunks of `chunk` entries and 32-entry tiles within a chunk.  far [R, S] (or
+    [R, S, 3]: any axis).  Returns the number of shaded entries, the tiles of every chunk, how many tiles hold at least
+    one far-node sample, how many hold none, and the far-node entries."""
+    if far.dim() == 3:
+        far = far.any(-1)
+    f = far.cpu()[shade_mask.cpu()]
+    n = f.numel()
+    e = torch.arange(n)
+    per_chunk = (chunk + 31) // 32
+    tile = (e // chunk) * per_chunk + (e % chunk) // 32
+    tiles = [(min(chunk, n - c) + 31) // 32 for c in range(0, n, chunk)]
+    hit = torch.zeros(max(1, per_chunk * len(tiles)), dtype=torch.bool)
+    hit[tile[f]] = True
+    nfar = int(hit.sum())
+    return dict(shaded=n, tiles=tiles, far_tiles=nfar, plain_tiles=sum(tiles) - nfar, far_entries=int(f.sum()))
 
 
 def factor_errors(G, T, M, F):

@@ -89,9 +89,12 @@ ROWS = {
 SHORT = (12, 9)   # the two short axes of a thin scene
 
 
-def _ndc_setup(grid, rays, seed):
+def _ndc_setup(grid, rays, seed, n_far_side=0):
     """thin LLFF-style NDC box (z in [-1, 1] is the long axis) and rays from the z = -1 plane: a bundle along z (the
-    first sample, t = near = 0, sits on the face), oblique rays, and rays grazing the long edges"""
+    first sample, t = near = 0, sits on the face), oblique rays, and rays grazing the long edges.  n_far_side: that many
+    more rays along z (appended, from a generator of their own: the other rays do not move) with x = +hx or y = +hy
+    (alternating) exactly -- every sample of such a ray is on that axis' far node; and the last sample (t = far = 1) of
+    every ray along z lands on z = +1, the far node of the long axis."""
     hx, hy = 0.1, 0.08
     aabb = [-hx, -hy, -1.0, hx, hy, 1.0]
     g = torch.Generator().manual_seed(seed)
@@ -104,6 +107,13 @@ def _ndc_setup(grid, rays, seed):
     o = torch.cat([xy, -torch.ones(na + no + ng, 1)], -1)
     dxy = torch.cat([torch.zeros(na, 2), 0.15 * torch.randn(no + ng, 2, generator=g)])
     d = torch.cat([dxy, 2.0 * torch.ones(na + no + ng, 1)], -1)
+    if n_far_side:
+        gf = torch.Generator().manual_seed(seed + 7919)
+        xy = lo + 2 * torch.tensor([hx, hy]) * torch.rand(n_far_side, 2, generator=gf)
+        xy[0::2, 0] = hx
+        xy[1::2, 1] = hy
+        o = torch.cat([o, torch.cat([xy, -torch.ones(n_far_side, 1)], -1)])
+        d = torch.cat([d, torch.tensor([0.0, 0.0, 2.0]).expand(n_far_side, 3)])
     return aabb, o.float().contiguous(), d.float().contiguous()
 
 

@@ -144,3 +144,73 @@ def test_single_contributions_of_a_long_line_are_caught():
         assert total >= 100, (name, total)
         # (measured: 82 %, 86 %, 87 % and 88 %; the misses are contributions below kappa 2^-24 of their texel)
         assert caught >= (0.4 if name.startswith("app_plane") else 0.75) * total, (name, caught, total)
+
+
+# ---- the far-node ray families of tests/test_gpu_pose_paths.py, on the fp32 oracle alone ------------------------------------
+# A sample on a far node (floor(ix) == size - 1) is where the pose gather must take the masked form of the interpolation; the
+# GPU rows count on these rays to put samples there.  If thin_box, UNIT or the families change so that the samples slip off
+# the nodes, these cases fail here -- the GPU rows would only lose their subject.
+def test_far_node_families_leave_existing_rays_alone():
+    for grid, rays, seed in (([12, 9, 72], (8, 16, 4, 3), 72), ([11, 9, 72], (8, 16, 4, 0), 63)):
+        aabb = P.thin_box(grid)
+        o0, d0 = P.ray_set(aabb, *rays[:3], n_miss=rays[3], seed=seed)
+        o1, d1 = P.ray_set(aabb, *rays[:3], n_miss=rays[3], seed=seed, n_far_side=6, n_far_entry=5)
+        n = sum(rays)
+        assert o1.shape[0] == n + 11 and torch.equal(o1[:n], o0) and torch.equal(d1[:n], d0)
+    from tests.test_gpu_scatter_shapes import _ndc_setup
+    _, o0, d0 = _ndc_setup([12, 9, 72], (8, 16, 4, 0), seed=3)
+    _, o1, d1 = _ndc_setup([12, 9, 72], (8, 16, 4, 0), seed=3, n_far_side=6)
+    assert o1.shape[0] == 34 and torch.equal(o1[:28], o0) and torch.equal(d1[:28], d0)
+
+
+def test_far_side_and_far_entry_rays_sit_on_far_nodes():
+    for grid, in_box in (([12, 9, 72], 2288), ([12, 9, 200], 6384), ([11, 9, 72], 2288)):
+        aabb = P.thin_box(grid)
+        S = 2 * (grid[2] - 1) + 9
+        o, d = P.ray_set(aabb, 0, 0, 0, seed=1, n_far_side=16)
+        valid, far = P.far_node_samples(aabb, grid, (0.5, 40.0), o, d, S)
+        assert int(valid.sum()) == in_box and (valid.sum(1) == in_box // 16).all(), grid
+        for k in range(16):   # alternating: x == hi (the 11- or 10-cell axis), y == hi (the 8-cell axis)
+            assert bool(far[k, :, k % 2][valid[k]].all()), (grid, k)
+            assert int(far[k, :, 2].sum()) == 1   # and the one sample on the far end face
+        o, d = P.ray_set(aabb, 0, 0, 0, seed=1, n_far_entry=16)
+        valid, far = P.far_node_samples(aabb, grid, (0.5, 40.0), o, d, S)
+        assert int(valid.sum()) == in_box, grid
+        assert bool(far[:, 0, 2].all()) and (far.any(-1).sum(1) == 1).all(), grid   # the first sample, and no other
+        # every full-length ray of the axial bundle ends on the far node of the long axis: one far-node sample per ray
+        o, d = P.ray_set(aabb, 8, 0, 0, seed=1)
+        _, far = P.far_node_samples(aabb, grid, (0.5, 40.0), o, d, S)
+        assert (far.any(-1).sum(1) == 1).all(), grid
+        # ... and none when S ends the bundle before the far face
+        _, far = P.far_node_samples(aabb, grid, (0.5, 40.0), o, d, 100)
+        assert not bool(far.any()), grid
+
+
+def test_ndc_far_side_rays_sit_on_far_nodes():
+    from tests.test_gpu_scatter_shapes import _ndc_setup
+    for grid in ([12, 9, 72], [12, 9, 1063]):
+        S = 2 * (grid[2] - 1) + 1
+        aabb, o, d = _ndc_setup(grid, (8, 0, 0, 0), seed=3, n_far_side=16)
+        valid, far = P.far_node_samples(aabb, grid, (0.0, 1.0), o, d, S, ndc=True)
+        assert bool(valid.all()), grid
+        for k in range(16):
+            assert bool(far[8 + k, :, k % 2].all()), (grid, k)
+        assert bool(far[:, -1, 2].all()), grid    # t = far = 1: z = +1
+        assert int(far[:8].any(-1).sum()) == 8, grid   # the plain bundle: that last sample only
+
+
+def test_census_counts_tiles_per_chunk():
+    far = torch.zeros(3, 100, dtype=torch.bool)
+    mask = torch.zeros(3, 100, dtype=torch.bool)
+    mask[0, :70] = True      # entries 0 .. 69
+    mask[2, 10:100] = True   # entries 70 .. 159
+    far[0, 5] = True         # entry 5: tile 0
+    far[1, 7] = True         # not shaded: no entry
+    far[2, 10] = True        # entry 70: tile 2 of one chunk; entry 6 = tile 0 of the second chunk of 64
+    far[2, 99] = True        # entry 159: the last tile
+    c = P.census(far, mask)
+    assert c == dict(shaded=160, tiles=[5], far_tiles=3, plain_tiles=2, far_entries=3), c
+    c = P.census(far, mask, chunk=64)
+    assert c == dict(shaded=160, tiles=[2, 2, 1], far_tiles=3, plain_tiles=2, far_entries=3), c
+    c = P.census(far[..., None].expand(3, 100, 3), torch.zeros_like(mask))
+    assert c == dict(shaded=0, tiles=[], far_tiles=0, plain_tiles=0, far_entries=0), c
