@@ -38,9 +38,10 @@ extern "C" {
  * jt_reg_losses_fused, removed jt_pose_fused* and redefined matrix-mode bit 2 at version 1100; 1200 = round 6: those changes,
  * jt_shade_lean_tape / jt_shade_set_lean_tape, the workspace no longer carries the tile lists unless that variant is selected;
  * 1201: + jt_chip_geometry; 1202: + jt_shade_workspace_layout; 1203: + jt_march_forward_pose / jt_march_backward_pose; 1204: +
- * jt_lattice_indices; 1205: + jt_ssim_forward / jt_ssim_workspace_bytes.  Additions bump the last two digits, anything a caller built against the old header would get wrong bumps the
+ * jt_lattice_indices; 1205: + jt_ssim_forward / jt_ssim_workspace_bytes; 1206: +
+ * jt_image_ingest / jt_image_ingest_workspace_bytes.  Additions bump the last two digits, anything a caller built against the old header would get wrong bumps the
  * hundreds). */
-#define JT_VERSION 1205
+#define JT_VERSION 1206
 
 #define JT_OK 0
 #define JT_ERR_ARG 1         /* null pointer / bad size */
@@ -444,6 +445,27 @@ int jt_tv_depth_forward(const float* depth, int n_views, int grid_h, int grid_w,
 int jt_ssim_forward(const float* pred, const float* target, int n_views, int n_channels, int height, int width, double* ssim,
                     float* ssim_map, void* workspace, size_t workspace_bytes, void* stream);
 size_t jt_ssim_workspace_bytes(int n_views, int n_channels, int height, int width);
+
+/* Picture preprocessing of the dataset loaders (data/base.py:92-107 `preprocess_image`, data/blender.py:71-76): n_images decoded
+ * pictures, uint8 [n_images][in_h][in_w][channels] (channels 3 or 4, device memory, 4-byte aligned when channels is 4) -> fp32
+ * [n_images][3][out_h][out_w] at `out`, EQUAL BIT FOR BIT to PIL.Image.resize((out_w, out_h), LANCZOS) of an 8-bit RGB / RGBA
+ * picture, torchvision's to_tensor (byte / 255 in fp32, IEEE division) and, for channels = 4 with `composite` set,
+ * rgb * mask + bgcolor * (1 - mask) in fp32, every operation rounded on its own (mask = the resampled alpha / 255); channels = 4
+ * without `composite` returns the resampled colour.  Pillow's arithmetic: RGBA is premultiplied ((t >> 8) + t) >> 8, t = c * a +
+ * 128, resampled, and divided out (c where a is 0 or 255, else min(255, 255 c / a)); each axis is a table of int32 weights in
+ * 2^22 fixed point, one output byte = clamp((2^21 + sum_i k_i in[first + i]) >> 22, 0, 255) in 32-bit integers; the horizontal
+ * pass first, rounded to bytes, then the vertical pass.  An axis whose sizes agree is skipped, and with both equal the picture
+ * is not premultiplied at all.  table_x / table_y (device, int32): [(2 + taps)][n_out], row 0 the first source index of every
+ * output index, row 1 its tap count (<= taps), row 2 + i the weight of tap i; built on the host in double precision
+ * (joint_tensorf_amd/datasets.py: resample_table); may be NULL for an axis whose sizes agree.  The kernels clamp every window to
+ * the picture.  workspace: jt_image_ingest_workspace_bytes(...) bytes (the byte intermediate of the horizontal pass; 0 when
+ * in_w == out_w), caller-provided, 4-byte aligned, overwritten.  One or two launches on `stream`, nothing else.  JT_ERR_ARG
+ * for channels outside {3, 4}, a size below 1, a missing table or a short workspace; JT_ERR_UNSUPPORTED for n_images > 65 535
+ * or more than 262 140 rows. */
+int jt_image_ingest(const uint8_t* images, int n_images, int in_h, int in_w, int channels, const int32_t* table_x, int taps_x,
+                    const int32_t* table_y, int taps_y, int out_h, int out_w, int composite, float bgcolor, float* out,
+                    void* workspace, size_t workspace_bytes, void* stream);
+size_t jt_image_ingest_workspace_bytes(int n_images, int in_h, int in_w, int channels, int out_h, int out_w);
 
 /* The weighted sum of Model.summarize_loss (model/tensorf.py:31-47) over the photometric term and the three
  * regularisers, one launch each way:  total = w_render render[0] + w_l1 reg3[0] + w_tv_density reg3[1] +

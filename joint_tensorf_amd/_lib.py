@@ -119,6 +119,8 @@ SIGNATURES = {
     "jt_tv_depth_forward": (I, [P, I, I, I, P, P]),
     "jt_ssim_forward": (I, [P, P, I, I, I, I, P, P, P, ctypes.c_size_t, P]),
     "jt_ssim_workspace_bytes": (ctypes.c_size_t, [I, I, I, I]),
+    "jt_image_ingest": (I, [P, I, I, I, I, P, I, P, I, I, I, I, F, P, P, ctypes.c_size_t, P]),
+    "jt_image_ingest_workspace_bytes": (ctypes.c_size_t, [I, I, I, I, I, I]),
     "jt_loss_sum_forward": (I, [P, P, F, F, F, F, P, P]),
     "jt_loss_sum_backward": (I, [P, F, F, F, F, P, P, P]),
     "jt_loss_sum_forward_dyn": (I, [P, P, P, P, P]),
@@ -174,7 +176,7 @@ def fused_lib():
 # the JT_VERSION of include/jt_render.h that SIGNATURES and the struct mirrors above were written against.  A constant, not a
 # read of the header at import time: a vendored copy of the package has no include/ directory beside it (tests/test_abi.py
 # holds this number, the header's and the library's together)
-JT_ABI_VERSION = 1205
+JT_ABI_VERSION = 1206
 
 
 def header_version():

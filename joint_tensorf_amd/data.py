@@ -69,8 +69,11 @@ class RenderedDataset(DictDataset):
 def load(opt, split, subset=None):
     """Which dataset object a run gets, recorded in `opt.data.dataset_class` and printed:
     * `opt.data.synthetic` = "rendered": RenderedDataset; any other true value ("noise"): SyntheticDataset;
-    * otherwise the reference's `data.<dataset>.Dataset` (this build dropped into the reference tree).  Only a MISSING
-      loader module falls back to the synthetic noise scene, loudly; a loader that is there and fails (wrong path, missing
+    * otherwise the reference's `data.<dataset>.Dataset` when such a module is importable (this build dropped into the
+      reference tree);
+    * no such module and `opt.data.root` set: the native loader of datasets.py (Blender / LLFF files read with PIL,
+      preprocessed on the device); a bad path, an unreadable file or a size mismatch raises;
+    * no such module and no root: the synthetic noise scene, loudly.  A loader that is there and fails (wrong path, missing
       dependency of its own, bad file) raises -- a run must not finish on noise images by accident."""
     syn = opt.data.get("synthetic", False)
     if syn:
@@ -84,9 +87,17 @@ def load(opt, split, subset=None):
         except ImportError as e:
             if getattr(e, "name", None) not in (name, "data"):
                 raise          # the loader exists; one of ITS imports is missing
+            mod = None
+            if opt.data.get("root", None):
+                from . import datasets
+                if opt.data.dataset not in datasets.NATIVE:
+                    raise ValueError("no native loader for data.dataset=%r (built: %s)" % (opt.data.dataset, ", ".join(sorted(datasets.NATIVE))))
+                ds = datasets.NATIVE[opt.data.dataset](opt, split=split, subset=subset)
+                opt.data.dataset_class = type(ds).__module__ + "." + type(ds).__name__
+                print("joint_tensorf_amd: %s split: %d views from %s (%s)" % (split, len(ds), ds.path, opt.data.dataset_class))
+                return ds
             print("joint_tensorf_amd: WARNING -- no dataset loader `%s` on the path (%s); %s split is the SYNTHETIC NOISE "
                   "scene (set opt.data.synthetic to choose it deliberately)" % (name, e, split))
-            mod = None
         ds = mod.Dataset(opt, split=split, subset=subset) if mod is not None \
             else SyntheticDataset(opt, split=split, subset=subset)
     opt.data.dataset_class = type(ds).__module__ + "." + type(ds).__name__

@@ -1177,6 +1177,44 @@ def ssim(pred, target, return_map=False):
     return (out, smap) if return_map else out
 
 
+_INGEST_TABLES = {}
+
+
+def _ingest_table(n_in, n_out, device):
+    """the coefficient table of one axis on the device (datasets.resample_table: host, double precision), kept per size pair:
+    a second call with the same sizes is launches only"""
+    key = (int(n_in), int(n_out), str(device))
+    if key not in _INGEST_TABLES:
+        from .datasets import resample_table
+        tab, taps = resample_table(n_in, n_out)
+        _INGEST_TABLES[key] = (torch.from_numpy(tab).to(device), taps)
+    return _INGEST_TABLES[key]
+
+
+def image_ingest(batch_u8, out, H, W, bgcolor=None):
+    """The loaders' picture preprocessing (data/base.py:92-107, data/blender.py:71-76) on the device: decoded pictures uint8
+    [B, h, w, c] (c = 3 or 4) -> fp32 [B, 3, H, W] written into `out` (a contiguous run of slots of the resident set), bit for bit
+    what Pillow's LANCZOS resize, to_tensor and -- for c = 4 and a `bgcolor` -- rgb * mask + bgcolor * (1 - mask) give on the host
+    (jt_image_ingest: one or two launches on the current stream).  Returns `out`."""
+    if batch_u8.dim() != 4 or batch_u8.dtype != torch.uint8 or batch_u8.shape[-1] not in (3, 4):
+        raise ValueError("image_ingest: pictures must be uint8 [B, h, w, 3 or 4] (got %s %s)" % (batch_u8.dtype, tuple(batch_u8.shape)))
+    B, h, w, c = batch_u8.shape
+    H, W = int(H), int(W)
+    if out.dtype != torch.float32 or tuple(out.shape) != (B, 3, H, W) or not out.is_contiguous():
+        raise ValueError("image_ingest: out must be contiguous fp32 %s (got %s %s)" % ((B, 3, H, W), out.dtype, tuple(out.shape)))
+    if B == 0:
+        return out
+    x = batch_u8.contiguous()
+    tx, kx = _ingest_table(w, W, x.device) if w != W else (None, 0)
+    ty, ky = _ingest_table(h, H, x.device) if h != H else (None, 0)
+    nbytes = lib.jt_image_ingest_workspace_bytes(B, h, w, c, H, W)
+    ws = torch.empty(max((nbytes + 3) // 4, 1), device=x.device, dtype=torch.int32)   # (the caching allocator: capturable)
+    check(lib.jt_image_ingest(ptr(x), B, h, w, c, ptr(tx), kx, ptr(ty), ky, H, W, int(bgcolor is not None and c == 4),
+                              float(bgcolor) if bgcolor is not None else 0.0, ptr(out), ptr(ws), ws.numel() * 4, _stream()),
+          "jt_image_ingest")
+    return out
+
+
 class LossSumDyn(torch.autograd.Function):
     """LossSum with the four weights read from device memory (`w4`, rewritten by the caller with poke_floats): the
     launch arguments of a captured hipGraph stay the same while the host schedule changes the weights."""

@@ -68,6 +68,57 @@ def load_options(name_or_path):
     return opt
 
 
+def _number(v):
+    """pyyaml reads `1e-3` (no dot) as a string: the reference converts such strings to float (options.py:38-53)"""
+    if isinstance(v, str):
+        try:
+            return float(v)
+        except ValueError:
+            return v
+    return v
+
+
+def parse_overrides(argv):
+    """The reference's dotted command-line overrides (options.py:17-57 `parse_arguments`): `--key.sub=value` -> nested Opt,
+    values read as yaml (`[40,40]`, `1.e-3`, `null`, `true`); `--key.sub=` is None, a bare `--key` true, `--key!` false."""
+    out = Opt()
+    for arg in argv:
+        if not arg.startswith("--"):
+            raise ValueError("override %r does not start with --" % arg)
+        key, eq, text = arg[2:].partition("=")
+        if eq:
+            value = yaml.safe_load(text)
+            value = [_number(e) for e in value] if isinstance(value, list) else _number(value)
+        else:
+            key, value = (key[:-1], False) if key.endswith("!") else (key, True)
+        parts = key.split(".")
+        if not key or any(not part for part in parts):
+            raise ValueError("override %r names no key" % arg)
+        node = out
+        for part in parts[:-1]:
+            if not isinstance(node.get(part, None), dict):
+                node[part] = Opt()
+            node = node[part]
+        if parts[-1] in node:
+            raise ValueError("%s is assigned twice" % key)
+        node[parts[-1]] = value
+    return out
+
+
+# top-level keys a run may set that no yaml of configs/ lists (read with opt.get by model/bat_hip.py and checkpoint.py)
+RUNTIME_KEYS = ("output_path", "load", "resume", "freq", "train_graph", "early_stop_iter", "device", "name", "group")
+
+
+def apply_overrides(opt, over):
+    """options.py:88-108 `override_options`: key by key, recursively.  The reference stops and asks at a key the yaml chain does
+    not know; here an unknown TOP-LEVEL key is an error (a typo must not silently train the defaults).  Below the top level new
+    keys are taken (data.root, data.train_sub, ... are run-time keys of their groups)."""
+    for k in over:
+        if k not in opt and k not in RUNTIME_KEYS:
+            raise KeyError("unknown option --%s (not a top-level key of the yaml chain; run-time keys: %s)" % (k, ", ".join(RUNTIME_KEYS)))
+    return _override(opt, over)
+
+
 def make_options(name, device="cuda", **overrides):
     """Load a config and fill the run-time fields the engine expects (opt.device, opt.H, opt.W)."""
     opt = load_options(name)
