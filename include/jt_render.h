@@ -39,9 +39,9 @@ extern "C" {
  * jt_shade_lean_tape / jt_shade_set_lean_tape, the workspace no longer carries the tile lists unless that variant is selected;
  * 1201: + jt_chip_geometry; 1202: + jt_shade_workspace_layout; 1203: + jt_march_forward_pose / jt_march_backward_pose; 1204: +
  * jt_lattice_indices; 1205: + jt_ssim_forward / jt_ssim_workspace_bytes; 1206: +
- * jt_image_ingest / jt_image_ingest_workspace_bytes.  Additions bump the last two digits, anything a caller built against the old header would get wrong bumps the
+ * jt_image_ingest / jt_image_ingest_workspace_bytes; 1207: + jt_shade_backward_plan / jt_march_backward_plan.  Additions bump the last two digits, anything a caller built against the old header would get wrong bumps the
  * hundreds). */
-#define JT_VERSION 1206
+#define JT_VERSION 1207
 
 #define JT_OK 0
 #define JT_ERR_ARG 1         /* null pointer / bad size */
@@ -350,10 +350,34 @@ int jt_shade_set_bwd_split(int run);
  * 20-channel scene -- and dBasis (the gradient of tensoRF.py:156's basis_mat) is formed inside the scatter kernel from the
  * products its walkers hold, instead of by a GEMM over recorded rows.  Same gradients up to the order of the float sums.
  * jt_shade_workspace_bytes / jt_shade_record_layout follow the mode; like the chunk size and the split mode it must not change
- * between a jt_shade_forward and its jt_shade_backward (the backward returns JT_ERR_ARG when it can tell).  The setter returns
- * the previous value; any argument other than 0 / 1 only queries. */
+ * between a jt_shade_forward and its jt_shade_backward (all of them take the tape from one function of the modes).  The setter
+ * returns the previous value; any argument other than 0 / 1 only queries. */
 int jt_shade_lean_tape(void);
 int jt_shade_set_lean_tape(int on);
+/* Which kernels jt_shade_backward would launch for this scene under the library's CURRENT modes (matrix mode, split, lean tape,
+ * deterministic mode, the JT_* environment switches) -- the launcher executes exactly this plan.  A diagnostic like
+ * jt_shade_workspace_layout: no device memory, no stream, nothing is launched.  want_factor_grads / want_mlp_grads: g_factors /
+ * g_mlp would be given; flags as for jt_shade_backward; have_aux: aux_stream and both events would be given.  out16:
+ *   [0]  split mode as requested, -1 resolved per scene kind (the tape and the caller's choice of streams follow this one)
+ *   [1]  split that runs: after the tile-owned scatter's fallback, the pose-only override (16) and the twelve-wave choice (8)
+ *   [2]  chain kernel k_shade_bwd<C, DET, SPLIT, B16>: 0 <C, false> (fused), 1 <C, true> (fused, deterministic),
+ *        2 <C, false, true> (split, fp32 matrix cores), 3 <C, false, true, true> (split, bf16 matrix cores)
+ *   [3]  second kernel: 0 none, 1 k_shade_scatter, 2 the tile-owned scatter, 3 k_pose_gather<C, false>, 4 k_pose_gather<C, true>
+ *   [4] [5] [6] [7]  DET, RUN, WAVES, FLAGS of k_shade_scatter<C, DET, RUN, WAVES, FLAGS> (0 unless [3] == 1)
+ *   [8]  its dynamic LDS bytes   [9] its workgroups at most (also the slab count k_dbasis_reduce sums)
+ *   [10] lean tape   [11] rows of a tile's record block (= jt_shade_record_layout out[0])
+ *   [12] dBasis is formed in the scatter
+ *   [13] weight-gradient GEMMs: 0 k_wgrad (fp32), 1 k_wgrad_b16   [14] GEMMs per chunk (0, 3 or 4)   [15] on the auxiliary stream
+ * JT_ERR_UNSUPPORTED for a NULL argument, a scene kind the shade kernels are not built for, or a plan without an instantiation. */
+int jt_shade_backward_plan(const JtScene* scene, int want_factor_grads, int want_mlp_grads, int flags, int have_aux,
+                           int32_t* out16);
+/* The same for jt_march_backward (want_factor_grads: g_factors given) / jt_march_backward_pose (have_dfeat = 1) on n_rays rays.
+ * out8:
+ *   [0] scan kernel k_march_bwd_scan<0 | 1 | 2>   [1] whether k_march_bwd_walk<Cd, DET, LINE, WAVES> runs behind it, and then
+ *   [2] runs per (ray, plane)   [3] LINE: 0 no LDS line, 1 a float copy, 2 doubles   [4] WAVES per workgroup
+ *   [5] the prefix table of the rays' item counts is kept in LDS (a run-time argument, no part of the kernel's name)
+ *   [6] dynamic LDS bytes   [7] workgroups */
+int jt_march_backward_plan(const JtScene* scene, int n_rays, int want_factor_grads, int have_dfeat, int32_t* out8);
 int jt_shade_forward(const JtScene* scene, const JtFactors* factors, const JtMlp* mlp, const float* rays_o,
                      const float* rays_d, const float* jitter, const float* zvals, const float* tmin,
                      const int32_t* shade_offset, int n_rays, const int32_t* entry_ray,

@@ -112,6 +112,8 @@ SIGNATURES = {
     "jt_shade_set_bwd_split": (I, [I]),
     "jt_shade_lean_tape": (I, []),
     "jt_shade_set_lean_tape": (I, [I]),
+    "jt_shade_backward_plan": (I, [SP, I, I, I, I, P]),
+    "jt_march_backward_plan": (I, [SP, I, I, I, P]),
     "jt_render_loss_forward": (I, [P, P, P, P, I, I, I, F, F, P, P, P]),
     "jt_render_loss_backward": (I, [P, P, P, P, I, I, I, F, F, P, P, P, P]),
     "jt_render_loss_forward_ind": (I, [P, P, P, I, I, I, I, F, F, P, P, P]),
@@ -176,7 +178,7 @@ def fused_lib():
 # the JT_VERSION of include/jt_render.h that SIGNATURES and the struct mirrors above were written against.  A constant, not a
 # read of the header at import time: a vendored copy of the package has no include/ directory beside it (tests/test_abi.py
 # holds this number, the header's and the library's together)
-JT_ABI_VERSION = 1206
+JT_ABI_VERSION = 1207
 
 
 def header_version():

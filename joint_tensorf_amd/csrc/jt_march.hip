@@ -5,6 +5,7 @@
 #include <cstdlib>
 
 #include "jt_common.h"
+#include "jt_plan.h"
 #include "jt_walk.h"
 
 namespace jt {
@@ -1026,6 +1027,143 @@ extern "C" size_t jt_march_backward_workspace_bytes(const JtScene* scene, int n_
   return march_bwd_ws_layout(scene->n_samples, n_rays, &a, &b);
 }
 
+// ---- the plan of the density backward: everything march_backward decides, from the knobs, the chip and the scene alone ---------
+static MarchBwdPlan plan_march_bwd(const Knobs& k, const Chip& chip, int S, int n_rays, int line_floats, int Cd, bool det,
+                                   bool want_factor_grads, bool have_dfeat) {
+  MarchBwdPlan P = {};
+  P.status = JT_OK;
+  const int Spad = (S + 63) & ~63;
+  const size_t scan_lds = (size_t)4 * (2 * Spad + (Spad >> 6)) * sizeof(float);
+  if (scan_lds > (size_t)kLdsBudget) return P.status = JT_ERR_UNSUPPORTED, P;
+  P.scan_lds = (int)scan_lds;
+  // nothing but the rays wants a gradient (test-time pose optimisation): the density path's coordinate gradient is taken in the
+  // scan kernel, lane per sample, and the walk is skipped (JT_POSE_BWD=0, read once: the walk with its targets switched off)
+  const bool pose_density = k.pose_bwd && !want_factor_grads && !det;
+  // (the stored derivatives serve the pose-only form; the walk gathers for itself)
+  P.scan = pose_density ? (have_dfeat ? 2 : 1) : 0;
+  P.walk = !pose_density;
+  P.cd = Cd, P.det = det;
+  if (!P.walk) return P;  // the ray gradients are complete: no walk, no fixed-point sums to add
+  P.runs = ((S + kWalkRun - 1) / kWalkRun + 3) & ~3;  // a wave's four groups: four runs of ONE (ray, plane)
+  const long witems = (long)n_rays * (P.runs / 4);
+  // JT_WALK_LDS_LINE (read once): 0 no LDS line, 1 a float copy, 2 a copy of doubles, unset: doubles where they fit the
+  // preferred workgroup shape, floats otherwise.  JT_WALK_WAVES = 8 / 16 forces the workgroup size.
+  const int lline_env = k.walk_lds_line, waves_env = k.walk_waves;
+  int nw = 8, lline = 0, prefix = 0;
+  size_t wlds = 0;
+  // a candidate (line mode, waves, two workgroups per CU wanted): its LDS bytes, or 0 when it does not fit
+  auto shape = [&](int lm, int w, bool two, int* pre) -> size_t {
+    const size_t rec_bytes = (size_t)w * 4 * (kWalkSub * kWalkRecW + 16) * sizeof(float);
+    size_t b = rec_bytes + (size_t)line_floats * sizeof(float) * lm;
+    if (b > 158 * 1024) return 0;
+    *pre = (n_rays <= kWalkPrefixRays && b + (size_t)n_rays * sizeof(int) <= 158 * 1024) ? 1 : 0;
+    if (*pre) b += (size_t)n_rays * sizeof(int);
+    if (two && 2 * (b + 256) > (size_t)kLdsBudget) return 0;
+    return b;
+  };
+  // eight-wave workgroups only where two of them fit a CU (otherwise sixteen waves: four per SIMD either way).  A shape that
+  // keeps the prefix table of the rays' item counts beats one that does not (without it the items come from a global counter,
+  // twice as slow): doubles with the table, floats with the table, then the same without it
+  const int modes[2] = {2, 1};
+  bool found = false;
+  const bool want_prefix = n_rays <= kWalkPrefixRays;
+  for (int need_pre = want_prefix ? 1 : 0; need_pre >= 0 && !found; --need_pre)
+    for (int mi = 0; mi < 2 && !found; ++mi) {
+      const int lm = modes[mi];
+      if (det || lline_env == 0 || (lline_env > 0 && lline_env != lm)) continue;
+      for (int w = 8; w <= 16 && !found; w += 8) {
+        if (waves_env == 8 || waves_env == 16) {
+          if (w != waves_env) continue;
+        }
+        int pre = 0;
+        const size_t b = shape(lm, w, w == 8 && waves_env != 8, &pre);
+        if (b && pre >= need_pre) nw = w, lline = lm, prefix = pre, wlds = b, found = true;
+      }
+    }
+  if (!found) {
+    for (int w = 8; w <= 16 && !found; w += 8) {
+      if ((waves_env == 8 || waves_env == 16) && w != waves_env) continue;
+      int pre = 0;
+      const size_t b = shape(0, w, w == 8 && waves_env != 8, &pre);
+      if (b) nw = w, lline = 0, prefix = pre, wlds = b, found = true;
+    }
+  }
+  if (!found) return P.status = JT_ERR_UNSUPPORTED, P;
+  P.line_mode = lline, P.waves = nw, P.prefix = prefix, P.lds = (int)wlds;
+  // (JT_WALK_WGS, read once: fewer workgroups -- a multiple of three -- leave CUs to whatever runs beside the walk)
+  // (one sixteen-wave / two eight-wave workgroups per CU, a multiple of three: 255 / 510 on MI355X's 256 CUs)
+  const long wg_full = (long)(chip.cus / 3 * 3) * (16 / nw);
+  const long wg_cap = k.walk_wgs > 0 ? std::min<long>(k.walk_wgs / 3 * 3, wg_full) : wg_full;
+  P.wgs = (int)std::min<long>(3 * ((witems + nw - 1) / nw), std::max<long>(wg_cap, 3));  // 85 / 170 workgroups per plane
+  return P;
+}
+
+// ---- launch code: one function template per kernel family, executing a plan ------------------------------------------------------
+template <int POSE, class... Args>
+static void launch_scan(int blocks, size_t lds, hipStream_t st, Args... args) {
+  static bool attr = false;
+  if (!attr) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_march_bwd_scan<POSE>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              kLdsBudget);
+    attr = true;
+  }
+  hipLaunchKernelGGL(k_march_bwd_scan<POSE>, dim3(blocks), dim3(256), lds, st, args...);
+}
+struct WalkArgs {
+  const Dev& D;
+  const JtFactors& G;
+  const float *rays_o, *rays_d, *jitter, *zvals, *tmin;
+  int n_rays;
+  const float* gfeat;
+  const uint16_t* vlist;
+  const int* nvalid;
+  int runs;
+  float *g_rays_o, *g_rays_d;
+  long long* rays_fixed;
+  unsigned* bad;
+  int line_words, prefix, wgs;
+  size_t lds;
+  hipStream_t st;
+};
+template <int CD, bool DET, int LLINE, int WAVES>
+static void launch_walk(const WalkArgs& a) {
+  static bool attr = false;
+  if (!attr) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_march_bwd_walk<CD, DET, LLINE, WAVES>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);  /* + 64 B static */
+    attr = true;
+  }
+  hipLaunchKernelGGL((k_march_bwd_walk<CD, DET, LLINE, WAVES>), dim3(a.wgs), dim3(WAVES * 64), a.lds, a.st, a.D, a.G, a.rays_o,
+                     a.rays_d, a.jitter, a.zvals, a.tmin, a.n_rays, a.gfeat, a.vlist, a.nvalid, a.runs, a.g_rays_o, a.g_rays_d,
+                     a.rays_fixed, a.bad, a.line_words, a.prefix);
+}
+// the k_march_bwd_walk shapes that exist: a plan (or a scene) whose shape is not listed is JT_ERR_UNSUPPORTED
+// (32 density components: no configuration of the reference's yamls has them, and two of that width's shapes spilled; the
+//  instantiations were removed in round 6 -- such a scene is JT_ERR_UNSUPPORTED here as it is in the shade kernels)
+struct WalkShape {
+  int cd;
+  bool det;
+  int line_mode, waves;
+  void (*launch)(const WalkArgs&);
+};
+template <int CD, bool DET, int LLINE, int WAVES>
+constexpr WalkShape walk_shape() { return {CD, DET, LLINE, WAVES, &launch_walk<CD, DET, LLINE, WAVES>}; }
+static const WalkShape* find_walk(const MarchBwdPlan& P) {
+  static const WalkShape l[16] = {
+      walk_shape<16, true, 0, 8>(),  walk_shape<16, true, 0, 16>(),  walk_shape<16, false, 0, 8>(), walk_shape<16, false, 0, 16>(),
+      walk_shape<16, false, 1, 8>(), walk_shape<16, false, 1, 16>(), walk_shape<16, false, 2, 8>(), walk_shape<16, false, 2, 16>(),
+      walk_shape<8, true, 0, 8>(),   walk_shape<8, true, 0, 16>(),   walk_shape<8, false, 0, 8>(),  walk_shape<8, false, 0, 16>(),
+      walk_shape<8, false, 1, 8>(),  walk_shape<8, false, 1, 16>(),  walk_shape<8, false, 2, 8>(),  walk_shape<8, false, 2, 16>()};
+  for (const WalkShape& w : l)
+    if (w.cd == P.cd && w.det == P.det && w.line_mode == P.line_mode && w.waves == P.waves) return &w;
+  return nullptr;
+}
+static int max_density_line_floats(const Dev& D) {
+  int line_floats = 0;
+  for (int a = 0; a < 3; ++a) line_floats = std::max(line_floats, D.ll[a] * D.Cd);
+  return line_floats;
+}
+
 static int march_backward(const JtScene* scene, const JtFactors* factors, const float* rays_o,
                           const float* rays_d, const float* jitter, const float* zvals, int n_rays,
                           const float* sigma_feat, const float* weight, const float* tmin,
@@ -1047,6 +1185,12 @@ static int march_backward(const JtScene* scene, const JtFactors* factors, const 
   if (workspace_bytes < march_bwd_ws_layout(D.S, n_rays, &o_vlist, &o_nvalid, &o_fixed)) return JT_ERR_ARG;
   // JT_DETERMINISTIC with factor gradients wanted: g_factors points at int64 shadow buffers, ray sums in fixed point
   const bool det = jt_deterministic() != 0;
+  const int line_floats = max_density_line_floats(D);
+  const MarchBwdPlan P = plan_march_bwd(knobs(), chip(), D.S, n_rays, line_floats, D.Cd, det, g_factors != nullptr,
+                                        dfeat_dn != nullptr);
+  if (P.status) return P.status;
+  const WalkShape* walk = nullptr;
+  if (P.walk && !(walk = find_walk(P))) return JT_ERR_UNSUPPORTED;
   long long* rays_fixed = reinterpret_cast<long long*>(reinterpret_cast<char*>(workspace) + o_fixed);
   JtFactors no_grads = {};  // g_factors == NULL: gradients w.r.t. the rays only (the walk writes no factor gradient)
   const JtFactors& GF = g_factors ? *g_factors : no_grads;
@@ -1054,129 +1198,51 @@ static int march_backward(const JtScene* scene, const JtFactors* factors, const 
   uint16_t* vlist = reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(workspace) + o_vlist);
   int* nvalid = reinterpret_cast<int*>(reinterpret_cast<char*>(workspace) + o_nvalid);
   const int Spad = (D.S + 63) & ~63;
-  const size_t lds = (size_t)4 * (2 * Spad + (Spad >> 6)) * sizeof(float);
-  if (lds > 160 * 1024) return JT_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
-  // nothing but the rays wants a gradient (test-time pose optimisation): the density path's coordinate gradient is taken in the
-  // scan kernel, lane per sample, and the walk is skipped (JT_POSE_BWD=0, read once: the walk with its targets switched off)
-  static const bool pose_env = [] { const char* e = getenv("JT_POSE_BWD"); return !e || atoi(e) != 0; }();
-  const bool pose_density = pose_env && !g_factors && !det;
-  if (!pose_density) dfeat_dn = nullptr;   // (the stored derivatives serve the pose-only form; the walk gathers for itself)
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_march_bwd_scan<0>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_march_bwd_scan<1>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_march_bwd_scan<2>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds);
-#define JT_SCAN_LAUNCH(POSE)                                                                                                   \
-  hipLaunchKernelGGL(k_march_bwd_scan<POSE>, dim3((n_rays + 3) / 4), dim3(256), lds, st, D, rays_o, rays_d, jitter, zvals,     \
-                     n_rays, sigma_feat, weight, tmin, shade_offset, shade_idx, rgb_s, clamp_mask, g_rgb, g_opacity,           \
-                     g_xyz_app, gfeat, vlist, nvalid, g_rays_o, g_rays_d, rays_fixed, Spad, dfeat_dn)
-  if (pose_density && dfeat_dn)
-    JT_SCAN_LAUNCH(2);
-  else if (pose_density)
-    JT_SCAN_LAUNCH(1);
+  if (P.scan != 2) dfeat_dn = nullptr;
+  const int sblocks = (n_rays + 3) / 4;
+  if (P.scan == 2)
+    launch_scan<2>(sblocks, P.scan_lds, st, D, rays_o, rays_d, jitter, zvals, n_rays, sigma_feat, weight, tmin, shade_offset,
+                   shade_idx, rgb_s, clamp_mask, g_rgb, g_opacity, g_xyz_app, gfeat, vlist, nvalid, g_rays_o, g_rays_d,
+                   rays_fixed, Spad, dfeat_dn);
+  else if (P.scan == 1)
+    launch_scan<1>(sblocks, P.scan_lds, st, D, rays_o, rays_d, jitter, zvals, n_rays, sigma_feat, weight, tmin, shade_offset,
+                   shade_idx, rgb_s, clamp_mask, g_rgb, g_opacity, g_xyz_app, gfeat, vlist, nvalid, g_rays_o, g_rays_d,
+                   rays_fixed, Spad, dfeat_dn);
   else
-    JT_SCAN_LAUNCH(0);
-#undef JT_SCAN_LAUNCH
+    launch_scan<0>(sblocks, P.scan_lds, st, D, rays_o, rays_d, jitter, zvals, n_rays, sigma_feat, weight, tmin, shade_offset,
+                   shade_idx, rgb_s, clamp_mask, g_rgb, g_opacity, g_xyz_app, gfeat, vlist, nvalid, g_rays_o, g_rays_d,
+                   rays_fixed, Spad, dfeat_dn);
   JT_LAUNCH_CHECK();
-  if (pose_density) return JT_OK;  // the ray gradients are complete: no walk, no fixed-point sums to add
+  if (!P.walk) return JT_OK;
   unsigned* bad = jt::fixed_bad_flag();
   if (!bad) return JT_ERR_ARG;
-  const int runs = ((D.S + kWalkRun - 1) / kWalkRun + 3) & ~3;  // a wave's four groups: four runs of ONE (ray, plane)
-  const long witems = (long)n_rays * (runs / 4);
-  int line_floats = 0;
-  for (int a = 0; a < 3; ++a) line_floats = std::max(line_floats, D.ll[a] * D.Cd);
-  // JT_WALK_LDS_LINE (read once): 0 no LDS line, 1 a float copy, 2 a copy of doubles, unset: doubles where they fit the
-  // preferred workgroup shape, floats otherwise.  JT_WALK_WAVES = 8 / 16 forces the workgroup size.
-  static const int lline_env = [] { const char* e = getenv("JT_WALK_LDS_LINE"); return e ? atoi(e) : -1; }();
-  static const int waves_env = [] { const char* e = getenv("JT_WALK_WAVES"); return e ? atoi(e) : 0; }();
-  int nw = 8, lline = 0, prefix = 0;
-  size_t wlds = 0;
-  // a candidate (line mode, waves, two workgroups per CU wanted): its LDS bytes, or 0 when it does not fit
-  auto shape = [&](int lm, int w, bool two, int* pre) -> size_t {
-    const size_t rec_bytes = (size_t)w * 4 * (kWalkSub * kWalkRecW + 16) * sizeof(float);
-    size_t b = rec_bytes + (size_t)line_floats * sizeof(float) * lm;
-    if (b > 158 * 1024) return 0;
-    *pre = (n_rays <= kWalkPrefixRays && b + (size_t)n_rays * sizeof(int) <= 158 * 1024) ? 1 : 0;
-    if (*pre) b += (size_t)n_rays * sizeof(int);
-    if (two && 2 * (b + 256) > 160 * 1024) return 0;
-    return b;
-  };
-  {
-    // eight-wave workgroups only where two of them fit a CU (otherwise sixteen waves: four per SIMD either way).  A shape that
-    // keeps the prefix table of the rays' item counts beats one that does not (without it the items come from a global counter,
-    // twice as slow): doubles with the table, floats with the table, then the same without it
-    const int modes[2] = {2, 1};
-    bool found = false;
-    const bool want_prefix = n_rays <= kWalkPrefixRays;
-    for (int need_pre = want_prefix ? 1 : 0; need_pre >= 0 && !found; --need_pre)
-      for (int mi = 0; mi < 2 && !found; ++mi) {
-        const int lm = modes[mi];
-        if (det || lline_env == 0 || (lline_env > 0 && lline_env != lm)) continue;
-        for (int w = 8; w <= 16 && !found; w += 8) {
-          if (waves_env == 8 || waves_env == 16) {
-            if (w != waves_env) continue;
-          }
-          int pre = 0;
-          const size_t b = shape(lm, w, w == 8 && waves_env != 8, &pre);
-          if (b && pre >= need_pre) nw = w, lline = lm, prefix = pre, wlds = b, found = true;
-        }
-      }
-    if (!found) {
-      for (int w = 8; w <= 16 && !found; w += 8) {
-        if ((waves_env == 8 || waves_env == 16) && w != waves_env) continue;
-        int pre = 0;
-        const size_t b = shape(0, w, w == 8 && waves_env != 8, &pre);
-        if (b) nw = w, lline = 0, prefix = pre, wlds = b, found = true;
-      }
-    }
-    if (!found) return JT_ERR_UNSUPPORTED;
-  }
-  // (JT_WALK_WGS, read once: fewer workgroups -- a multiple of three -- leave CUs to whatever runs beside the walk)
-  static const int wgs_env = [] { const char* e = getenv("JT_WALK_WGS"); return e ? atoi(e) : 0; }();
-  // (one sixteen-wave / two eight-wave workgroups per CU, a multiple of three: 255 / 510 on MI355X's 256 CUs)
-  const long wg_full = (long)(chip().cus / 3 * 3) * (16 / nw);
-  const long wg_cap = wgs_env > 0 ? std::min<long>(wgs_env / 3 * 3, wg_full) : wg_full;
-  const int blocks = (int)std::min<long>(3 * ((witems + nw - 1) / nw), std::max<long>(wg_cap, 3));  // 85 / 170 workgroups per plane
-#define JT_WALK_ONE(CD_, DET_, LL_, NW_)                                                                                    \
-  do {                                                                                                                      \
-    static bool attr = false;                                                                                               \
-    if (!attr) {                                                                                                            \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_march_bwd_walk<CD_, DET_, LL_, NW_>),                       \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);  /* + 64 B static */               \
-      attr = true;                                                                                                          \
-    }                                                                                                                       \
-    hipLaunchKernelGGL((k_march_bwd_walk<CD_, DET_, LL_, NW_>), dim3(blocks), dim3(NW_ * 64), wlds, st, D, GF, rays_o,      \
-                       rays_d, jitter, zvals, tmin, n_rays, gfeat, vlist, nvalid, runs, g_rays_o, g_rays_d, rays_fixed,     \
-                       bad, lline * line_floats, prefix);                                                               \
-  } while (0)
-#define JT_WALK_NW(CD_, DET_, LL_)              \
-  do {                                          \
-    if (nw == 8) JT_WALK_ONE(CD_, DET_, LL_, 8); \
-    else JT_WALK_ONE(CD_, DET_, LL_, 16);       \
-  } while (0)
-#define JT_WALK(CD_)                               \
-  do {                                             \
-    if (det) JT_WALK_NW(CD_, true, 0);             \
-    else if (lline == 2) JT_WALK_NW(CD_, false, 2); \
-    else if (lline == 1) JT_WALK_NW(CD_, false, 1); \
-    else JT_WALK_NW(CD_, false, 0);                \
-  } while (0)
-  if (D.Cd == 16) JT_WALK(16);
-  else if (D.Cd == 8) JT_WALK(8);
-  // (32 density components: no configuration of the reference's yamls has them, and two of that width's shapes spilled; the
-  //  instantiations were removed in round 6 -- such a scene is JT_ERR_UNSUPPORTED here as it is in the shade kernels)
-  else return JT_ERR_UNSUPPORTED;
-#undef JT_WALK
-#undef JT_WALK_NW
-#undef JT_WALK_ONE
+  const WalkArgs a = {D, GF, rays_o, rays_d, jitter, zvals, tmin, n_rays, gfeat, vlist, nvalid, P.runs, g_rays_o, g_rays_d,
+                      rays_fixed, bad, P.line_mode * line_floats, P.prefix, P.wgs, (size_t)P.lds, st};
+  walk->launch(a);
   JT_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_rays_fixed_add, dim3((n_rays * 6 + 255) / 256), dim3(256), 0, st, rays_fixed, n_rays, g_rays_o,
                      g_rays_d, bad, g_status_word.load(std::memory_order_relaxed));
   JT_LAUNCH_CHECK();
   return JT_OK;
 }
+
+// The plan jt_march_backward (want_factor_grads) / jt_march_backward_pose (have_dfeat) would execute for this scene and ray
+// count under the library's current modes (jt_render.h has the indices); needs no device memory and no stream
+extern "C" int jt_march_backward_plan(const JtScene* scene, int n_rays, int want_factor_grads, int have_dfeat, int32_t* out8) {
+  Dev D;
+  if (!out8 || make_dev(scene, nullptr, &D) || check_density_shape(D)) return JT_ERR_UNSUPPORTED;
+  if (n_rays < 1) return JT_ERR_ARG;
+  const bool det = jt_deterministic() != 0;
+  const MarchBwdPlan P = plan_march_bwd(knobs(), chip(), D.S, n_rays, max_density_line_floats(D), D.Cd, det,
+                                        want_factor_grads != 0, have_dfeat != 0);
+  if (P.status) return P.status;
+  if (P.walk && !find_walk(P)) return JT_ERR_UNSUPPORTED;
+  const int32_t v[8] = {P.scan, P.walk, P.runs, P.line_mode, P.waves, P.prefix, P.lds, P.wgs};
+  for (int i = 0; i < 8; ++i) out8[i] = v[i];
+  return JT_OK;
+}
+
 extern "C" int jt_march_backward(const JtScene* scene, const JtFactors* factors, const float* rays_o,
                                  const float* rays_d, const float* jitter, const float* zvals, int n_rays,
                                  const float* sigma_feat, const float* weight, const float* tmin,

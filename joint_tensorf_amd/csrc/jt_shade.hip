@@ -14,9 +14,11 @@
 // row stride => conflict-free) simply reads the matching column.  The gather is split the same way:
 // half h loads the channel quads q with q % 2 == h as 16-byte vectors.
 #include <atomic>
+#include <climits>
 #include <cstdlib>
 
 #include "jt_common.h"
+#include "jt_plan.h"
 #include "jt_walk.h"
 
 #include "jt_shade_core.h"
@@ -1692,19 +1694,51 @@ __global__ __launch_bounds__(256) void k_wgrad_reduce4(const float* __restrict__
 
 using namespace jt;
 
-// which stages run on the bf16 matrix cores with three-piece operands (fp32-level accuracy, jt_shade_core.h): bit 0 the
-// forward chain (k_shade_fwd_b16), bit 1 the weight-gradient GEMMs (k_wgrad_b16), bit 2 the chain of the SPLIT backward
-// (k_shade_bwd<..., SPLIT, B16>).  JT_BF16X3 (read once) overrides the build
-// default; 0 = everything on the fp32 matrix cores.
-static std::atomic<int> g_matrix_mode{-1};
-static int bf16x3_mode() {
-  int m = g_matrix_mode.load(std::memory_order_relaxed);
-  if (m < 0) {
-    const char* e = getenv("JT_BF16X3");
-    m = (e ? atoi(e) : JT_BF16X3_DEFAULT) & 7;
-    g_matrix_mode.store(m, std::memory_order_relaxed);
-  }
-  return m;
+// ---- the knob record (jt_plan.h): every environment variable of the two backwards is read HERE, once ---------------------------
+static int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+static Knobs read_env_knobs() {
+  Knobs k;
+  // which stages run on the bf16 matrix cores with three-piece operands (fp32-level accuracy, jt_shade_core.h): bit 0 the
+  // forward chain (k_shade_fwd_b16), bit 1 the weight-gradient GEMMs (k_wgrad_b16), bit 2 the chain of the SPLIT backward
+  // (k_shade_bwd<..., SPLIT, B16>).  JT_BF16X3 overrides the build default; 0 = everything on the fp32 matrix cores.
+  k.matrix_mode = env_int("JT_BF16X3", JT_BF16X3_DEFAULT) & 7;
+  k.split = env_int("JT_BWD_SPLIT", -1);
+  if (k.split != 0 && k.split != 1 && k.split != 8 && k.split != 16) k.split = -1;
+  k.lean = env_int("JT_LEAN_TAPE", 1) ? 1 : 0;
+  // shaded samples per backward launch (and per set of weight-gradient GEMMs)
+  k.chunk_log2 = env_int("JT_SHADE_CHUNK_LOG2", 22);  // measured: 2^20 4.48 ms / step, 2^21 4.34, 2^22 4.33 (fewer launches, slabs and tails)
+  if (k.chunk_log2 < 16 || k.chunk_log2 > 22) k.chunk_log2 = 22;
+  k.scatter_wgs = std::max(env_int("JT_SCATTER_WGS", 0), 0);
+  k.scatter_waves = env_int("JT_SCATTER_WAVES", 0);
+  k.scatter_flags = env_int("JT_SCATTER_FLAGS", 1) & 1;
+  k.scatter_first = env_int("JT_SCATTER_FIRST", 0) != 0;
+  k.wgrad_pipe = env_int("JT_WGRAD_PIPE", 1) != 0;
+  k.ablate = env_int("JT_ABLATE", 0);
+  k.pose_bwd = env_int("JT_POSE_BWD", 1) != 0;
+  k.tile_wgs = env_int("JT_TILE_WGS", 0);
+  if (k.tile_wgs < 6) k.tile_wgs = 0;
+  k.tile_ratio = env_int("JT_TILE_RATIO", 0);
+  if (k.tile_ratio <= 0 || k.tile_ratio >= 100) k.tile_ratio = 62;
+  k.walk_lds_line = env_int("JT_WALK_LDS_LINE", -1);
+  k.walk_waves = env_int("JT_WALK_WAVES", 0);
+  k.walk_wgs = env_int("JT_WALK_WGS", 0);
+  return k;
+}
+// what the four setters have stored (kUnset: the environment's value stands)
+static const int kUnset = INT_MIN;
+static std::atomic<int> g_matrix_mode{kUnset}, g_bwd_split{kUnset}, g_lean{kUnset}, g_chunk_log2{kUnset};
+Knobs jt::knobs() {
+  static const Knobs env = read_env_knobs();
+  Knobs k = env;
+  int v;
+  if ((v = g_matrix_mode.load(std::memory_order_relaxed)) != kUnset) k.matrix_mode = v;
+  if ((v = g_bwd_split.load(std::memory_order_relaxed)) != kUnset) k.split = v;
+  if ((v = g_lean.load(std::memory_order_relaxed)) != kUnset) k.lean = v;
+  if ((v = g_chunk_log2.load(std::memory_order_relaxed)) != kUnset) k.chunk_log2 = v;
+  return k;
 }
 
 typedef ShadeCfg<48, 27, 64, JT_MLP_FEA> CfgBlender;     // bat_blender_VM: VM-48, MLP_Fea 150->64->64->3
@@ -1718,21 +1752,6 @@ static int shade_kind(const JtScene* s) {
   return -1;
 }
 
-// workspace = [tile-blocked records of every chunk of shaded samples | per-(chunk, block) partial weight
-// gradients].  Every chunk has its own record block so that the weight-gradient GEMMs of all chunks can run
-// on an auxiliary stream, concurrently with whatever the caller enqueues next on the main stream (the
-// density backward: atomics / VALU bound, while the GEMMs are MFMA bound).
-// shaded samples per backward launch (and per set of weight-gradient GEMMs); JT_SHADE_CHUNK_LOG2 overrides (16..22)
-static int g_chunk_log2 = 0;  // 0 = not yet initialised from the environment
-static int chunk_entries() {
-  if (!g_chunk_log2) {
-    const char* e = getenv("JT_SHADE_CHUNK_LOG2");
-    int l = e ? atoi(e) : 22;  // measured: 2^20 4.48 ms / step, 2^21 4.34, 2^22 4.33 (fewer launches, slabs and tails)
-    if (l < 16 || l > 22) l = 22;
-    g_chunk_log2 = l;
-  }
-  return 1 << g_chunk_log2;
-}
 #if JT_STAMP
 extern "C" int jt_debug_read_stamps(unsigned long long* out8) {
   if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_stamps), 8 * sizeof(unsigned long long)) != hipSuccess) return JT_ERR_ARG;
@@ -1741,41 +1760,6 @@ extern "C" int jt_debug_read_stamps(unsigned long long* out8) {
   return JT_OK;
 }
 #endif
-// Split appearance backward: 0 = one kernel (chain + scatter in k_shade_bwd), 8 / 16 = k_shade_bwd<SPLIT> + k_shade_scatter
-// with runs of that many samples per 16-lane group, 1 = k_shade_bwd<SPLIT> + the TILE-OWNED scatter of jt_tile.h (pairs binned
-// by plane tile, gradient slices in matrix-core registers), -1 = per scene kind (the default): split 16 for the 20-channel
-// WeakView scene (bat_llff_VM_MLP: its line gradients, privatised in LDS by the scatter kernel, are 40 % of the fused kernel's
-// time: 0.49 -> 0.35 ms per launch) and, since the chain runs on the bf16 matrix cores (round 5: 508 -> 281 us), for VM-48 as
-// well (281 + 994 against 1 365 us fused; with the fp32 chain the fused kernel wins: profiles/round4_bwd_split_ablation.txt).
-// JT_BWD_SPLIT (read once) overrides.
-static std::atomic<int> g_bwd_split{-2};
-// Workgroups of k_shade_scatter (persistent, one per CU: its LDS fills the CU).  The scatter's time is inversely proportional to
-// its workgroups (256: 0.96 ms, 192: 1.25, 128: 1.88): the float-atomic path is a PER-CU limit.  All the same the 48-channel
-// scatter runs on 192 CUs -- 24 per XCD -- while the weight-gradient GEMMs are forked beside it: their 262-368 registers do not
-// fit on a CU that holds a scatter workgroup, on 256 scatter workgroups they start when the scatter ends and the launch stream
-// idles ~0.39 ms at the join; with 8 CUs per XCD to themselves they are done when the longer scatter is -- 3.00 against 3.07 ms
-// per step, six alternating repeats (188 / 196 workgroups, which do not divide by the XCDs, lose 2-5 %; the 20-channel scene,
-// whose GEMMs are small, loses 2 % and keeps 256; profiles/round5_scatter_beside_gemms.txt).  JT_SCATTER_WGS (read once) overrides.
-// Round 6: with dBasis formed in the scatter itself only three GEMMs (1.7 instead of 2.5 GB of record rows) run beside it and the
-// balance moves to 224 workgroups = 28 per XCD = 7 per shader engine: 2.88 against 2.93 (192) and 2.97 ms (256) per step
-// (profiles/round6_lean_tape_ab.txt).
-// (the counts are those of a full MI355X -- 256 CUs in 8 XCDs --; Chip::wgs scales them to the device the library runs on)
-// Later in round 6: the twelve-wave scatter (three waves per SIMD, runs of 8) is faster per CU and hands the GEMMs 64 CUs again:
-// 192 workgroups, 2.81 against 2.85-2.89 ms per step (profiles/round6_scatter_12_waves.txt).
-static int scatter_wgs(bool gemms_beside, bool lean = false, bool w12 = false) {
-  static const int v = [] { const char* e = getenv("JT_SCATTER_WGS"); const int n = e ? atoi(e) : 0; return n > 0 ? n : 0; }();
-  return v ? std::min(v, chip().cus) : chip().wgs(gemms_beside ? ((lean && !w12) ? 224 : 192) : 256);
-}
-static int bwd_split_mode() {
-  int m = g_bwd_split.load(std::memory_order_relaxed);
-  if (m < -1) {
-    const char* e = getenv("JT_BWD_SPLIT");
-    m = e ? atoi(e) : -1;
-    if (m != 0 && m != 1 && m != 8 && m != 16) m = -1;
-    g_bwd_split.store(m, std::memory_order_relaxed);
-  }
-  return m;
-}
 #if JT_TILE_STAMP
 extern "C" int jt_debug_read_tile_stamps(unsigned long long* out16) {
   if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_tstamps), 16 * sizeof(unsigned long long)) != hipSuccess) return JT_ERR_ARG;
@@ -1784,80 +1768,87 @@ extern "C" int jt_debug_read_tile_stamps(unsigned long long* out16) {
   return JT_OK;
 }
 #endif
+// Split appearance backward: 0 = one kernel (chain + scatter in k_shade_bwd), 8 / 16 = k_shade_bwd<SPLIT> + k_shade_scatter
+// with runs of that many samples per 16-lane group, 1 = k_shade_bwd<SPLIT> + the TILE-OWNED scatter of jt_tile.h (pairs binned
+// by plane tile, gradient slices in matrix-core registers), -1 = per scene kind (the default): split 16 for the 20-channel
+// WeakView scene (bat_llff_VM_MLP: its line gradients, privatised in LDS by the scatter kernel, are 40 % of the fused kernel's
+// time: 0.49 -> 0.35 ms per launch) and, whenever the chain runs on the bf16 matrix cores (matrix-mode bit 2; round 5: 508 ->
+// 281 us), for VM-48 as well (281 + 994 against 1 365 us fused; with the fp32 chain, 508 + 994, the fused kernel wins and
+// stays: profiles/round4_bwd_split_ablation.txt).  JT_BWD_SPLIT (read once) overrides.
+template <class C>
+static int split_default(const Knobs& k) { return (C::CA < 48 || (k.matrix_mode & 4)) ? 16 : 0; }
 // "Lean tape" (round 6; JT_LEAN_TAPE, read once, default 1; jt_shade_set_lean_tape): when the backward is the split form with the
 // walker scatter (runs of 8 / 16), dBasis is formed inside k_shade_scatter and the training forward does not record the 3 Ca
 // plane x line products -- a tile's record block shrinks from REC_FLOATS to R_LEAN rows (neither are the G2 rows stored: k_wgrad XA).  Whether a render is lean is a function
 // of the library's modes alone (this switch, the split mode, matrix-mode bit 2), so the forward, the backward and the workspace
-// query agree as long as no mode changes between a forward and its backward (as for jt_shade_set_chunk_log2).
-static std::atomic<int> g_lean{-1};
-static int lean_mode() {
-  int m = g_lean.load(std::memory_order_relaxed);
-  if (m < 0) {
-    const char* e = getenv("JT_LEAN_TAPE");
-    m = (e ? atoi(e) : 1) ? 1 : 0;
-    g_lean.store(m, std::memory_order_relaxed);
-  }
-  return m;
+// queries agree as long as no mode changes between a forward and its backward (as for jt_shade_set_chunk_log2): all of them
+// take the tape from THIS function.
+struct ShadeTape {
+  int split_requested;  // the split mode with -1 resolved
+  bool lean;
+  int rows;             // rows of a tile's record block
+};
+template <class C>
+static ShadeTape shade_tape(const Knobs& k) {
+  ShadeTape t;
+  t.split_requested = k.split >= 0 ? k.split : split_default<C>(k);
+  t.lean = k.lean && (t.split_requested == 8 || t.split_requested == 16);
+  t.rows = t.lean ? BwdCfg<C>::R_LEAN : BwdCfg<C>::REC_FLOATS;
+  return t;
 }
-template <class C>
-static int split_default() { return (C::CA < 48 || (bf16x3_mode() & 4)) ? 16 : 0; }
-template <class C>
-static bool lean_tape() {
-  if (!lean_mode()) return false;
-  const int m = bwd_split_mode();
-  return m == 8 || m == 16 || (m == -1 && split_default<C>() != 0);
-}
-template <class C>
-static int rec_rows() { return lean_tape<C>() ? BwdCfg<C>::R_LEAN : BwdCfg<C>::REC_FLOATS; }
-extern "C" int jt_shade_lean_tape(void) { return lean_mode(); }
+extern "C" int jt_shade_lean_tape(void) { return knobs().lean; }
 extern "C" int jt_shade_set_lean_tape(int on) {
-  const int prev = lean_mode();
+  const int prev = knobs().lean;
   if (on == 0 || on == 1) g_lean.store(on, std::memory_order_relaxed);
   return prev;
 }
-extern "C" int jt_shade_bwd_split(void) { return bwd_split_mode(); }
+extern "C" int jt_shade_bwd_split(void) { return knobs().split; }
 extern "C" int jt_shade_set_bwd_split(int run) {
-  const int prev = bwd_split_mode();
+  const int prev = knobs().split;
   if (run == -1 || run == 0 || run == 1 || run == 8 || run == 16) g_bwd_split.store(run, std::memory_order_relaxed);
   return prev;
 }
-extern "C" int jt_shade_chunk_entries(void) { return chunk_entries(); }
-extern "C" int jt_shade_matrix_mode(void) { return bf16x3_mode(); }
+extern "C" int jt_shade_chunk_entries(void) { return 1 << knobs().chunk_log2; }
+extern "C" int jt_shade_matrix_mode(void) { return knobs().matrix_mode; }
 extern "C" int jt_shade_set_matrix_mode(int mode) {
-  const int prev = bf16x3_mode();
+  const int prev = knobs().matrix_mode;
   if (mode >= 0 && mode <= 7) g_matrix_mode.store(mode, std::memory_order_relaxed);
   return prev;
 }
 // returns the previous log2; values outside 16..22 only query.  The caller re-sizes its workspace afterwards
 // (jt_shade_workspace_bytes depends on the chunk size); not to be changed between a forward and its backward.
 extern "C" int jt_shade_set_chunk_log2(int log2_entries) {
-  (void)chunk_entries();
-  const int prev = g_chunk_log2;
-  if (log2_entries >= 16 && log2_entries <= 22) g_chunk_log2 = log2_entries;
+  const int prev = knobs().chunk_log2;
+  if (log2_entries >= 16 && log2_entries <= 22) g_chunk_log2.store(log2_entries, std::memory_order_relaxed);
   return prev;
 }
-#define kChunkEntries (chunk_entries())
-static const int kNoGradRecords = 1 << 8;  // internal flag of launch_shade_bwd
+static const int kNoGradRecords = 1 << 8;  // internal flag of jt_shade_backward
 static const int kWgradBlocks = 512;
 
+// workspace = [tile-blocked records of every chunk of shaded samples | per-(chunk, block) partial weight
+// gradients].  Every chunk has its own record block so that the weight-gradient GEMMs of all chunks can run
+// on an auxiliary stream, concurrently with whatever the caller enqueues next on the main stream (the
+// density backward: atomics / VALU bound, while the GEMMs are MFMA bound).
 template <class C>
 struct WsLayout {
   typedef BwdCfg<C> B;
   typedef WgradDims<C> WD;
   static constexpr int NT3 = WD::NT3, NT1 = WD::NT1, NTB = WD::NTB;
   static constexpr size_t P3 = WD::P3, P2 = WD::P2, P1 = WD::P1, PB = WD::PB;
-  static size_t rec_floats_per_chunk() { return (size_t)rec_rows<C>() * kChunkEntries; }
+  const int rows;         // of a tile's record block (shade_tape)
+  const int chunk;        // shaded samples per backward launch
+  const bool tile_lists;  // the tile-owned scatter is selected
+  explicit WsLayout(const Knobs& k) : rows(shade_tape<C>(k).rows), chunk(1 << k.chunk_log2), tile_lists(k.split == 1) {}
+  size_t rec_floats_per_chunk() const { return (size_t)rows * chunk; }
   static size_t slab_floats_per_chunk() { return (P3 + P2 + P1 + PB) * kWgradBlocks; }
   // records of all chunks are one contiguous tile-blocked array (a chunk is a whole number of 32-sample tiles), so
   // they take what `cap` samples need, not whole chunks; the slabs follow
-  static size_t rec_floats(int cap) { return (size_t)rec_rows<C>() * (((size_t)std::max(cap, 1) + 31) / 32 * 32); }
+  size_t rec_floats(int cap) const { return (size_t)rows * (((size_t)std::max(cap, 1) + 31) / 32 * 32); }
   // (the tile-owned scatter's lists exist only while that variant is selected: up to 0.7 GB nobody else reads)
-  static size_t bytes(int cap) {
-    return main_bytes(cap) + (bwd_split_mode() == 1 ? tile_ws_bytes(cap, kChunkEntries) : 0);
-  }
+  size_t bytes(int cap) const { return main_bytes(cap) + (tile_lists ? tile_ws_bytes(cap, chunk) : 0); }
   // records + slabs; the tile-owned scatter's lists and counters (jt_tile.h) sit behind them
-  static size_t main_bytes(int cap) {
-    const int nchunks = (int)(((long)cap + kChunkEntries - 1) / kChunkEntries);
+  size_t main_bytes(int cap) const {
+    const int nchunks = (int)(((long)cap + chunk - 1) / chunk);
     return (rec_floats(cap) + slab_floats_per_chunk() * (size_t)std::max(nchunks, 1)) * sizeof(float);
   }
 };
@@ -1869,7 +1860,8 @@ static const int kMaxEntries = 1 << 30;
 extern "C" size_t jt_shade_workspace_bytes(const JtScene* scene, int n_entries_max) {
   const int kind = shade_kind(scene);
   if (kind < 0 || n_entries_max < 1 || n_entries_max > kMaxEntries) return 0;
-  return (kind == 0) ? WsLayout<CfgBlender>::bytes(n_entries_max) : WsLayout<CfgLlff>::bytes(n_entries_max);
+  const Knobs k = knobs();
+  return (kind == 0) ? WsLayout<CfgBlender>(k).bytes(n_entries_max) : WsLayout<CfgLlff>(k).bytes(n_entries_max);
 }
 
 // Where the pieces of a shade workspace sit, for the library's CURRENT modes (tests/test_sanitizers.py: every carved piece must
@@ -1881,21 +1873,21 @@ extern "C" size_t jt_shade_workspace_bytes(const JtScene* scene, int n_entries_m
 //          list, gx, items, cnt, offs, cursor, ctl in out[9..22]
 template <class C>
 static void ws_layout(int cap, int64_t* out) {
-  typedef WsLayout<C> W;
-  const int chunk = kChunkEntries;
+  const WsLayout<C> W(knobs());
+  const int chunk = W.chunk;
   const int nchunks = std::max((int)(((long)cap + chunk - 1) / chunk), 1);
-  out[0] = (int64_t)W::bytes(cap);
-  out[1] = (int64_t)(W::rec_floats(cap) * sizeof(float));
+  out[0] = (int64_t)W.bytes(cap);
+  out[1] = (int64_t)(W.rec_floats(cap) * sizeof(float));
   out[2] = out[1];
-  out[3] = (int64_t)(W::slab_floats_per_chunk() * sizeof(float));
+  out[3] = (int64_t)(W.slab_floats_per_chunk() * sizeof(float));
   out[4] = nchunks;
-  out[5] = rec_rows<C>();
-  out[6] = (int64_t)((W::P3 + W::P2 + W::P1) * kWgradBlocks * sizeof(float));
+  out[5] = W.rows;
+  out[6] = (int64_t)((W.P3 + W.P2 + W.P1) * kWgradBlocks * sizeof(float));
   out[7] = (int64_t)((size_t)chip().cus * ScatCfg<C>::DB_SLAB * sizeof(float));
-  out[8] = bwd_split_mode() == 1 ? 1 : 0;
+  out[8] = W.tile_lists ? 1 : 0;
   for (int i = 9; i < 23; ++i) out[i] = 0;
   if (out[8]) {
-    const TileWs t = tile_ws_carve(reinterpret_cast<void*>((uintptr_t)W::main_bytes(cap)), cap, chunk);
+    const TileWs t = tile_ws_carve(reinterpret_cast<void*>((uintptr_t)W.main_bytes(cap)), cap, chunk);
     const size_t lc = (size_t)t.list_cap, mi = (size_t)t.max_items;
     const void* ptrs[7] = {t.list, t.gx, t.items, t.cnt, t.offs, t.cursor, t.ctl};
     const size_t sizes[7] = {3 * lc * sizeof(uint4), kTileMaxClasses * lc * sizeof(float4), 3 * mi * sizeof(int4),
@@ -1920,10 +1912,11 @@ extern "C" int jt_shade_workspace_layout(const JtScene* scene, int n_entries_max
 extern "C" int jt_shade_record_layout(const JtScene* scene, int32_t* out) {
   const int kind = shade_kind(scene);
   if (kind < 0 || !out) return JT_ERR_UNSUPPORTED;
+  const Knobs k = knobs();
   if (kind == 0) {
-    out[0] = rec_rows<CfgBlender>(); out[1] = BwdCfg<CfgBlender>::R_MASK; out[2] = CfgBlender::HID;
+    out[0] = shade_tape<CfgBlender>(k).rows; out[1] = BwdCfg<CfgBlender>::R_MASK; out[2] = CfgBlender::HID;
   } else {
-    out[0] = rec_rows<CfgLlff>(); out[1] = BwdCfg<CfgLlff>::R_MASK; out[2] = CfgLlff::HID;
+    out[0] = shade_tape<CfgLlff>(k).rows; out[1] = BwdCfg<CfgLlff>::R_MASK; out[2] = CfgLlff::HID;
   }
   out[3] = 32;
   return JT_OK;
@@ -1933,17 +1926,18 @@ template <class C, int REC>
 static int launch_shade_fwd_t(const Dev& D, const MlpDev& M, const PeMask& pm, const float* rays_o,
                               const float* rays_d, const float* jitter, const float* zvals, const float* tmin,
                               const int32_t* offset, int R, const int32_t* eray, const int32_t* esmp,
-                              const float* vdir, float* rgb_s, float* rec, int cap, hipStream_t st) {
+                              const float* vdir, float* rgb_s, float* rec, int cap, const Knobs& k, hipStream_t st) {
   long tiles = ((long)cap + 31) / 32;
-  // JT_BF16X3 (read once): the forward's matrix stages as six bf16 MFMAs per fp32 product sum (jt_shade_core.h)
-  if (bf16x3_mode() & 1) {
+  const int rows = shade_tape<C>(k).rows;
+  // matrix-mode bit 0: the forward's matrix stages as six bf16 MFMAs per fp32 product sum (jt_shade_core.h)
+  if (k.matrix_mode & 1) {
     const size_t lds16 = B16Cfg<C>::LDS_BYTES;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_shade_fwd_b16<C, REC>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16);
     constexpr int NW = JT_B16_THREADS / 64;
     int blocks16 = (int)std::min<long>((tiles + NW - 1) / NW, chip().cus);   // one 115 KB-LDS workgroup per CU
     hipLaunchKernelGGL((k_shade_fwd_b16<C, REC>), dim3(blocks16), dim3(JT_B16_THREADS), lds16, st, D, M, pm, rays_o, rays_d, jitter,
-                       zvals, tmin, offset, R, eray, esmp, vdir, rgb_s, rec, cap, rec_rows<C>());
+                       zvals, tmin, offset, R, eray, esmp, vdir, rgb_s, rec, cap, rows);
     JT_LAUNCH_CHECK();
     return JT_OK;
   }
@@ -1952,7 +1946,7 @@ static int launch_shade_fwd_t(const Dev& D, const MlpDev& M, const PeMask& pm, c
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   int blocks = (int)std::min<long>((tiles + 3) / 4, 512);
   hipLaunchKernelGGL((k_shade_fwd<C, REC>), dim3(blocks), dim3(256), lds, st, D, M, pm, rays_o, rays_d, jitter, zvals,
-                     tmin, offset, R, eray, esmp, vdir, rgb_s, rec, cap, rec_rows<C>());
+                     tmin, offset, R, eray, esmp, vdir, rgb_s, rec, cap, rows);
   JT_LAUNCH_CHECK();
   return JT_OK;
 }
@@ -1965,19 +1959,20 @@ static int launch_shade_fwd(const Dev& D, const MlpDev& M, const PeMask& pm, con
                             const int32_t* offset, int R, const int32_t* eray, const int32_t* esmp,
                             const float* vdir, float* rgb_s, int cap, float* ws, size_t ws_bytes, int flags,
                             hipStream_t st) {
+  const Knobs k = knobs();
   if (ws) {
-    if (ws_bytes < WsLayout<C>::bytes(cap)) return JT_ERR_ARG;
+    if (ws_bytes < WsLayout<C>(k).bytes(cap)) return JT_ERR_ARG;
     if (flags & JT_SHADE_POSE_ONLY)
       return launch_shade_fwd_t<C, 2>(D, M, pm, rays_o, rays_d, jitter, zvals, tmin, offset, R, eray, esmp, vdir,
-                                      rgb_s, ws, cap, st);
-    if (lean_tape<C>())
+                                      rgb_s, ws, cap, k, st);
+    if (shade_tape<C>(k).lean)
       return launch_shade_fwd_t<C, 3>(D, M, pm, rays_o, rays_d, jitter, zvals, tmin, offset, R, eray, esmp, vdir,
-                                      rgb_s, ws, cap, st);
+                                      rgb_s, ws, cap, k, st);
     return launch_shade_fwd_t<C, 1>(D, M, pm, rays_o, rays_d, jitter, zvals, tmin, offset, R, eray, esmp, vdir,
-                                    rgb_s, ws, cap, st);
+                                    rgb_s, ws, cap, k, st);
   }
   return launch_shade_fwd_t<C, 0>(D, M, pm, rays_o, rays_d, jitter, zvals, tmin, offset, R, eray, esmp, vdir,
-                                  rgb_s, nullptr, cap, st);
+                                  rgb_s, nullptr, cap, k, st);
 }
 
 extern "C" int jt_shade_forward(const JtScene* scene, const JtFactors* factors, const JtMlp* mlp, const float* rays_o,
@@ -2024,7 +2019,8 @@ struct TileSel {
   static int tiles(int H, int W) { return tiles_along(W) * tiles_along(H); }
   template <int CFG>
   static int launch(const Dev& D, const MlpDev& M, const JtFactors& G, const TileWs& TW, const int32_t* offset, int R,
-                    float* g_xyz, const float* rc, int start, int ccap, int cap, int line_len, hipStream_t st) {
+                    float* g_xyz, const float* rc, int start, int ccap, int cap, int line_len, int nwg, int ratio,
+                    hipStream_t st) {
     constexpr int SPLIT = CFG == 0 ? SPLIT0 : 0;
     constexpr int WAVES = CFG == 0 ? 16 : 8;
     constexpr int NCLS = SPLIT ? 2 : 1;
@@ -2043,11 +2039,8 @@ struct TileSel {
         return JT_ERR_UNSUPPORTED;
       attr = lds;
     }
-    // workgroups: one per CU, dealt to the (plane, class) sets; a class of two channel groups gets JT_TILE_RATIO per cent of
+    // workgroups (nwg: one per CU, or JT_TILE_WGS), dealt to the (plane, class) sets; a class of two channel groups gets `ratio` (JT_TILE_RATIO) per cent of
     // its plane's share (the per-pair set-up -- list entry, GF rows, tap records -- is the same for both classes)
-    static const int nwg_env = [] { const char* e = getenv("JT_TILE_WGS"); const int v = e ? atoi(e) : 0; return v >= 6 ? v : 0; }();
-    const int nwg = nwg_env ? nwg_env : std::max(chip().cus, 6);
-    static const int ratio = [] { const char* e = getenv("JT_TILE_RATIO"); const int v = e ? atoi(e) : 0; return (v > 0 && v < 100) ? v : 62; }();
     TileClasses TC;
     int acc = 0;
     for (int pl = 0; pl < 3; ++pl) {
@@ -2067,131 +2060,92 @@ struct TileSel {
   }
 };
 
+// ---- the plan of the appearance backward: everything launch_shade_bwd decides, from the knobs, the chip and the scene alone -----
+// dynamic LDS of k_shade_scatter<C, .., RUN, WAVES, FLAGS>: the basis^T image, the LDS line (FLAGS bit 0), the dBasis sum
+// (FLAGS bit 1) and the waves' step records
 template <class C>
-static int launch_shade_bwd(const Dev& D, const MlpDev& M, const PeMask& pm, const JtFactors& G, const JtMlp& GM,
-                            const int32_t* offset, int R, const float* rgb_s, const float* g_rgb_s, float* g_xyz,
-                            int cap,
-                            float* ws, size_t ws_bytes, int flags, hipStream_t st, hipStream_t aux,
-                            hipEvent_t ev_fork, hipEvent_t ev_join) {
-  typedef BwdCfg<C> B;
-  typedef WsLayout<C> W;
-  const size_t lds = B::LDS_FLOATS * sizeof(float);
-  if (lds > 160 * 1024) return JT_ERR_UNSUPPORTED;
-  if (ws_bytes < W::bytes(cap)) return JT_ERR_ARG;
-  const int chunk = kChunkEntries;
-  const int nchunks = (int)(((long)cap + chunk - 1) / chunk);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_shade_bwd<C, false>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_shade_bwd<C, true>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  float* recs = ws;
-  float* slabs = ws + W::rec_floats(cap);
-  const size_t cstride = W::slab_floats_per_chunk();
-  const int nb = kWgradBlocks;
-  // profiling knob, read ONCE per process: 1 = no scatter, 2 = no gradient records, 4 = no weight-gradient GEMMs
-  static const int abl_env = [] { const char* e = getenv("JT_ABLATE"); return e ? atoi(e) : 0; }();
-  const int det = jt_deterministic();  // 16: the appearance-factor gradients go to int64 shadow buffers (fixed point)
-  // (bit 5: lean tape -- the chain does not store the G2 rows)
-  const int ablate = abl_env | ((flags & JT_SHADE_SKIP_WGRAD) ? 4 : 0) |
-                     ((flags & kNoGradRecords) ? 2 : 0) | (det ? 16 : 0) | (lean_tape<C>() ? 32 : 0);
-  constexpr int NT3 = W::NT3, NT1 = W::NT1, NTB = W::NTB;
-  constexpr int XF1 = (C::KIND == JT_MLP_FEA) ? 1 : 2;
-  // ---- per chunk: the per-sample backward on the main stream, its weight-gradient GEMMs on the auxiliary stream ----
-  // (the GEMMs of chunk c stream the records of chunk c while the backward of chunk c + 1 runs: the backward holds
-  //  one 155 KB-LDS workgroup per CU at two waves per SIMD, the GEMMs need no LDS and fit beside it)
-  const bool use_aux = aux && ev_fork && ev_join && !(ablate & 4);
-  static const bool pipe = [] { const char* e = getenv("JT_WGRAD_PIPE"); return !e || atoi(e) != 0; }();
-  hipStream_t ws_st = use_aux ? aux : st;
-  const int RR = rec_rows<C>();   // rows of a tile's record block (lean tape: without the product rows)
-  // per scene kind (-1): split 16 whenever the chain runs on the bf16 matrix cores (matrix-mode bit 2) -- the 20-channel scene
-  // always did; VM-48 since round 5: chain 281 us + scatter 994 against 1 365 fused (with the fp32 chain, 508 + 994, the fused
-  // kernel wins and stays)
-  const int split_dflt = split_default<C>();
-  int split = bwd_split_mode() >= 0 ? bwd_split_mode() : split_dflt;
-  unsigned* bad = jt::fixed_bad_flag();
-  if (!bad) return JT_ERR_ARG;
+static size_t scatter_lds_bytes(int line_floats, bool dbs, int run, int flags, int waves) {
+  return (size_t)(ScatCfg<C>::BT_FLOATS + ((flags & 1) ? line_floats : 0) + (dbs ? ScatCfg<C>::RED_FLOATS : 0) +
+                  waves * ScatCfg<C>::wave_floats(run, dbs)) * sizeof(float);
+}
+// Workgroups of k_shade_scatter (persistent, one per CU: its LDS fills the CU).  The scatter's time is inversely proportional to
+// its workgroups (256: 0.96 ms, 192: 1.25, 128: 1.88): the float-atomic path is a PER-CU limit.  All the same the 48-channel
+// scatter runs on 192 CUs -- 24 per XCD -- while the weight-gradient GEMMs are forked beside it: their 262-368 registers do not
+// fit on a CU that holds a scatter workgroup, on 256 scatter workgroups they start when the scatter ends and the launch stream
+// idles ~0.39 ms at the join; with 8 CUs per XCD to themselves they are done when the longer scatter is -- 3.00 against 3.07 ms
+// per step, six alternating repeats (188 / 196 workgroups, which do not divide by the XCDs, lose 2-5 %; the 20-channel scene,
+// whose GEMMs are small, loses 2 % and keeps 256; profiles/round5_scatter_beside_gemms.txt).  JT_SCATTER_WGS (read once) overrides.
+// Round 6: with dBasis formed in the scatter itself only three GEMMs (1.7 instead of 2.5 GB of record rows) run beside it and the
+// balance moves to 224 workgroups = 28 per XCD = 7 per shader engine: 2.88 against 2.93 (192) and 2.97 ms (256) per step
+// (profiles/round6_lean_tape_ab.txt).
+// (the counts are those of a full MI355X -- 256 CUs in 8 XCDs --; Chip::wgs scales them to the device the library runs on)
+// Later in round 6: the twelve-wave scatter (three waves per SIMD, runs of 8) is faster per CU and hands the GEMMs 64 CUs again:
+// 192 workgroups, 2.81 against 2.85-2.89 ms per step (profiles/round6_scatter_12_waves.txt).
+static int scatter_wgs(const Knobs& k, const Chip& chip, bool gemms_beside, bool dbs, bool w12) {
+  return k.scatter_wgs ? std::min(k.scatter_wgs, chip.cus) : chip.wgs(gemms_beside ? ((dbs && !w12) ? 224 : 192) : 256);
+}
+
+template <class C>
+static ShadeBwdPlan plan_shade_bwd(const Knobs& k, const Chip& chip, const ShadeBwdInputs& in) {
+  typedef TileSel<C> TS;
+  ShadeBwdPlan P = {};
+  P.status = JT_OK;
+  if (BwdCfg<C>::LDS_FLOATS * sizeof(float) > (size_t)kLdsBudget) P.status = JT_ERR_UNSUPPORTED;
+  const ShadeTape tape = shade_tape<C>(k);
+  P.split_requested = tape.split_requested;
+  P.lean = tape.lean;
+  P.rec_rows = tape.rows;
+  const bool det = in.det;  // the appearance-factor gradients go to int64 shadow buffers (fixed point)
+  // no MLP gradients wanted: nobody will read the gradient records, and there is nothing for the GEMMs to form
+  const bool no_records = !in.want_mlp_grads || (in.flags & kNoGradRecords);
+  // the kernels' `ablate` argument: JT_ABLATE (profiling: 1 = no scatter, 2 = no gradient records, 4 = no weight-gradient
+  // GEMMs), bit 4 deterministic mode, bit 5 lean tape -- the chain does not store the G2 rows
+  P.ablate = k.ablate | (((in.flags & JT_SHADE_SKIP_WGRAD) || !in.want_mlp_grads) ? 4 : 0) | (no_records ? 2 : 0) |
+             (det ? 16 : 0) | (tape.lean ? 32 : 0);
+  // the GEMMs of chunk c stream the records of chunk c on the auxiliary stream while the backward of chunk c + 1 runs: the
+  // backward holds one 155 KB-LDS workgroup per CU at two waves per SIMD, the GEMMs need no LDS and fit beside it
+  P.gemm_forked = in.have_aux && !(P.ablate & 4);
+  P.gemm_pipe = k.wgrad_pipe != 0;
+  P.gemm_b16 = (k.matrix_mode & 2) != 0;
+  // (JT_SCATTER_FIRST=1: the scatter in front of the fork, as in the fused kernel's order)
+  P.scatter_first = k.scatter_first != 0;
+  int split = tape.split_requested;
   // tile-owned scatter (split == 1): needs factor gradients to write, float accumulation, a scene whose tiles and LDS line fit
   // what the kernel and the workspace are sized for -- otherwise the scene kind's default takes over
-  typedef TileSel<C> TS;
-  int tile_line_len = 0;
-  for (int a = 0; a < 3; ++a) tile_line_len = std::max(tile_line_len, D.ll[a]);
   // (one workgroup shape since round 6: eight waves, one channel class; the sixteen-wave two-class shape of round 5 spilled
   //  184-264 bytes per lane, took 2.7-3.4 ms and was removed -- a line too long for this shape falls back to the walker scatter)
-  const int tile_cfg = 1;
+  for (int a = 0; a < 3; ++a) P.tile_line_len = std::max(P.tile_line_len, in.line_len[a]);
   if (split == 1) {
-    bool ok = !det && G.app_plane[0] && G.app_line[0] && TS::lds_bytes(tile_cfg, tile_line_len) <= 160 * 1024;
-    for (int a = 0; a < 3 && ok; ++a) ok = TS::tiles(D.ph[a], D.pw[a]) <= kTileMaxTiles;
-    if (!ok) split = split_dflt;
+    bool ok = !det && in.want_factor_grads && TS::lds_bytes(1, P.tile_line_len) <= (size_t)kLdsBudget;
+    for (int a = 0; a < 3 && ok; ++a) ok = TS::tiles(in.plane_h[a], in.plane_w[a]) <= kTileMaxTiles;
+    if (!ok) split = split_default<C>(k);
   }
   const bool tile = (split == 1);
-  const TileWs TW = tile_ws_carve(reinterpret_cast<char*>(ws) + W::main_bytes(cap), cap, chunk);
-  // fused: one kernel per chunk.  Split: the chain (launch_bwd) and the scatter (launch_scatter) -- the weight-gradient GEMMs only
-  // need the chain's records, so they are forked BEHIND THE CHAIN and run next to the atomic-bound scatter.
-  // nothing but the rays wants a gradient (no factor gradients, no weight gradients): the walker-free kernel
+  P.tile_wgs = k.tile_wgs ? k.tile_wgs : std::max(chip.cus, 6);
+  P.tile_ratio = k.tile_ratio;
+  // nothing but the rays wants a gradient (no factor gradients, no weight gradients): the chain alone (k_shade_bwd<SPLIT>: GF
+  // rows out), then the walker-free k_pose_gather in the scatter's place
   // (JT_POSE_BWD=0, read once: the fused kernel with its scatter switched to "no targets", as before round 5)
-  static const bool pose_env = [] { const char* e = getenv("JT_POSE_BWD"); return !e || atoi(e) != 0; }();
-  const bool pose_only = pose_env && !det && !G.app_plane[0] && !G.app_line[0] && (flags & kNoGradRecords) && (ablate & 4);
-  if (pose_only) split = 16;  // the chain alone (k_shade_bwd<SPLIT>: GF rows out), then k_pose_gather in the scatter's place
-  // lean tape: the forward recorded no products, dBasis comes out of the walker scatter (k_shade_scatter FLAGS bit 1)
-  const bool lean = lean_tape<C>();
-  if (lean && (split != 8 && split != 16)) return JT_ERR_ARG;  // (a mode was changed between the forward and this backward)
-  const bool dbs = lean && !pose_only && !(ablate & 4) && GM.basis != nullptr;
-  // (the scatter's workgroups leave their dBasis slices where the fourth GEMM's slabs used to go)
-  if (dbs && (size_t)chip().cus * ScatCfg<C>::DB_SLAB > W::PB * (size_t)kWgradBlocks) return JT_ERR_UNSUPPORTED;
-  auto launch_bwd = [&](int ci) -> int {
-    const int start = ci * chunk, ccap = std::min(chunk, cap - start);
-    long tiles = ((long)ccap + 31) / 32;
-    int blocks = (int)std::min<long>((tiles + B::NWAVE - 1) / B::NWAVE, chip().cus);   // one workgroup per CU (its LDS fills it)
-    float* rc = recs + W::rec_floats_per_chunk() * ci;
-    if (split && (bf16x3_mode() & 4)) {
-      // the chain of the split backward on the bf16 matrix cores (three-piece operands): matrix-mode bit 2
-      const size_t lds_b = ((BwdB16Cfg<C>::IMG_BYTES + 15) & ~(size_t)15) + (size_t)B::NWAVE * B::STASH_FLOATS * sizeof(float);
-      static bool attr_b = false;
-      if (!attr_b) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_shade_bwd<C, false, true, true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b);
-        attr_b = true;
-      }
-      hipLaunchKernelGGL((k_shade_bwd<C, false, true, true>), dim3(blocks), dim3(512), lds_b, st, D, M, pm, G, offset, R, rgb_s,
-                         g_rgb_s, g_xyz, rc, start, ccap, cap, ablate, bad, RR);
-    } else if (split) {
-      const size_t lds_c = B::LDS_FLOATS_SPLIT * sizeof(float);
-      static bool attr_done = false;
-      if (!attr_done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_shade_bwd<C, false, true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c);
-        attr_done = true;
-      }
-      hipLaunchKernelGGL((k_shade_bwd<C, false, true>), dim3(blocks), dim3(512), lds_c, st, D, M, pm, G, offset, R, rgb_s,
-                         g_rgb_s, g_xyz, rc, start, ccap, cap, ablate, bad, RR);
-    } else if (det) {
-      hipLaunchKernelGGL((k_shade_bwd<C, true>), dim3(blocks), dim3(512), lds, st, D, M, pm, G, offset, R, rgb_s,
-                         g_rgb_s, g_xyz, rc, start, ccap, cap, ablate, bad, RR);
-    } else {
-      hipLaunchKernelGGL((k_shade_bwd<C, false>), dim3(blocks), dim3(512), lds, st, D, M, pm, G, offset, R, rgb_s,
-                         g_rgb_s, g_xyz, rc, start, ccap, cap, ablate, bad, RR);
-    }
-    JT_LAUNCH_CHECK();
-    return JT_OK;
-  };
+  P.pose_only = k.pose_bwd && !det && !in.want_factor_grads && no_records && (P.ablate & 4);
+  if (P.pose_only) split = 16;
+  // lean tape: the forward recorded no products, dBasis comes out of the walker scatter (k_shade_scatter FLAGS bit 1); its
+  // workgroups leave their dBasis slices where the fourth GEMM's slabs used to go
+  const bool dbs = tape.lean && !P.pose_only && !(P.ablate & 4) && in.want_mlp_grads;
+  if (dbs && (size_t)chip.cus * ScatCfg<C>::DB_SLAB > WgradDims<C>::PB * (size_t)kWgradBlocks) P.status = JT_ERR_UNSUPPORTED;
   // JT_SCATTER_FLAGS (read once): bit 0 line gradients through LDS (k_shade_scatter)
-  static const int sflags_env = [] { const char* e = getenv("JT_SCATTER_FLAGS"); return e ? atoi(e) & 1 : 1; }();
+  for (int a = 0; a < 3; ++a) P.line_floats = std::max(P.line_floats, in.line_len[a] * C::CA);
+  int sflags = split ? k.scatter_flags : 0;
+  if (det) sflags &= ~1;
+  auto lds_of = [&](int run, int fl, int sw) { return scatter_lds_bytes<C>(P.line_floats, dbs, run, fl, sw); };
   // waves per scatter workgroup, ONE workgroup per CU: two waves per SIMD (8) reach the atomic unit's rate on VM-48; the
   // 20-channel scatter runs at 40 % of that rate (latency of the walk, not atomics) and takes four per SIMD (16) where the LDS
   // line still fits beside their step records (runs of 8)
-  int line_floats = 0;
-  for (int a = 0; a < 3; ++a) line_floats = std::max(line_floats, D.ll[a] * C::CA);
-  int sflags = split ? sflags_env : 0;
-  if (det) sflags &= ~1;
-  auto scatter_lds = [&](int run, int fl, int sw) {
-    return (size_t)(ScatCfg<C>::BT_FLOATS + ((fl & 1) ? line_floats : 0) + (dbs ? ScatCfg<C>::RED_FLOATS : 0) +
-                    sw * ScatCfg<C>::wave_floats(run, dbs)) * sizeof(float);
-  };
-  static const int sw_env = [] { const char* e = getenv("JT_SCATTER_WAVES"); return e ? atoi(e) : 0; }();
-  int sw = 8;
   // (with dBasis formed in the scatter the sixteen-wave shape's 128 registers spill 44-96 bytes per lane -- and it is still the
   //  faster shape where it fits: LLFF stage 0, 20 480 rays, 4.01 against 4.24 ms per step with eight waves)
-  if (C::CA < 48 && split && !tile && (sw_env == 16 || (sw_env == 0 && scatter_lds(split, sflags, 16) <= 160 * 1024))) sw = 16;
+  int sw = 8;
+  if (C::CA < 48 && split && !tile &&
+      (k.scatter_waves == 16 || (k.scatter_waves == 0 && lds_of(split, sflags, 16) <= (size_t)kLdsBudget)))
+    sw = 16;
   // The 48-channel scatter at THREE waves per SIMD (round 6): twelve-wave workgroups, runs of 8 (the step records of runs of 16
   // do not fit beside the LDS line twelve times), 168 registers with the basis^T operands read from LDS at their use (12 bytes of
   // scratch remain).  The kernel waits on memory for half of its wave cycles (SQ counters, profiles/round6_held_flush_experiment.txt),
@@ -2199,134 +2153,279 @@ static int launch_shade_bwd(const Dev& D, const MlpDev& M, const PeMask& pm, con
   // 192 workgroups beside the three GEMMs the step 2.85-2.89 -> 2.81 ms.  Chosen when the split mode is left to the library
   // (or JT_BWD_SPLIT=8 JT_SCATTER_WAVES=12), dBasis is formed in the kernel, accumulation is float and the line fits;
   // JT_SCATTER_WAVES=8 keeps the eight-wave shape.
-  bool w12 = false;
   // (the 20-channel scene gains nothing from it: final LLFF grid, scatter 0.288 ms in both shapes -- its instantiation was removed)
-  if (C::CA >= 48 && !det && !tile && !pose_only && dbs && sflags == 1 && (sw_env == 0 || sw_env == 12) &&
-      ((bwd_split_mode() == -1 && split == 16) || (bwd_split_mode() == 8 && sw_env == 12)) &&
-      scatter_lds(8, sflags, 12) <= 160 * 1024) {
+  bool w12 = false;
+  if (C::CA >= 48 && !det && !tile && !P.pose_only && dbs && sflags == 1 && (k.scatter_waves == 0 || k.scatter_waves == 12) &&
+      ((k.split == -1 && split == 16) || (k.split == 8 && k.scatter_waves == 12)) &&
+      lds_of(8, sflags, 12) <= (size_t)kLdsBudget) {
     split = 8, sw = 12, w12 = true;
   }
-  if (split && !tile && scatter_lds(split, sflags, sw) > 160 * 1024) sflags &= ~1;  // a line too long for the LDS: global atomics as before
-  auto launch_scatter = [&](int ci) -> int {
-    if (!split || (ablate & 1)) return JT_OK;
+  if (split && !tile && lds_of(split, sflags, sw) > (size_t)kLdsBudget) sflags &= ~1;  // a line too long for the LDS: global atomics as before
+  P.split = split;
+  // fused: one kernel per chunk.  Split: the chain and the second kernel -- the weight-gradient GEMMs only need the chain's
+  // records, so they are forked BEHIND THE CHAIN and run next to the atomic-bound scatter.
+  // (matrix-mode bit 2: the chain of the split backward on the bf16 matrix cores, three-piece operands)
+  P.chain = split ? ((k.matrix_mode & 4) ? kChainSplitB16 : kChainSplit) : (det ? kChainFusedDet : kChainFused);
+  P.chain_lds = (int)(P.chain == kChainSplitB16 ? ((BwdB16Cfg<C>::IMG_BYTES + 15) & ~(size_t)15) +
+                                                      (size_t)BwdCfg<C>::NWAVE * BwdCfg<C>::STASH_FLOATS * sizeof(float)
+                      : P.chain == kChainSplit  ? BwdCfg<C>::LDS_FLOATS_SPLIT * sizeof(float)
+                                                : BwdCfg<C>::LDS_FLOATS * sizeof(float));
+  if (!split || (P.ablate & 1)) P.second = kSecondNone;
+  else if (P.pose_only)
+    // (the 20-channel scene keeps the fp32 product: its bf16 instantiation needs 168 registers + 8 bytes of scratch at three
+    //  waves per SIMD, for a product that is a third of VM-48's)
+    P.second = ((k.matrix_mode & 4) && C::CA >= 48) ? kSecondPoseGatherB16 : kSecondPoseGather;
+  else P.second = tile ? kSecondTile : kSecondScatter;
+  if (P.second == kSecondScatter) {
+    P.sc_det = det, P.sc_run = split, P.sc_waves = sw, P.sc_flags = (sflags & 1) | (dbs ? 2 : 0);
+    P.sc_lds = (int)lds_of(split, sflags, sw);
+    P.sc_wgs = scatter_wgs(k, chip, P.gemm_forked && C::CA >= 48, dbs, w12);
+  }
+  P.dbasis_in_scatter = dbs;
+  P.gemm_count = (P.ablate & 4) ? 0 : (dbs ? 3 : 4);
+  return P;
+}
+
+// ---- launch code: one function template per kernel family, executing a plan ------------------------------------------------------
+// each sets the dynamic-LDS attribute of its instantiation once and launches; the caller checks hipGetLastError
+template <class C, bool DET, bool SPLIT, bool B16, class... Args>
+static void launch_chain(int blocks, size_t lds, hipStream_t st, Args... args) {
+  static bool attr = false;
+  if (!attr) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_shade_bwd<C, DET, SPLIT, B16>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    attr = true;
+  }
+  hipLaunchKernelGGL((k_shade_bwd<C, DET, SPLIT, B16>), dim3(blocks), dim3(512), lds, st, args...);
+}
+
+struct ScatterArgs {
+  const Dev& D;
+  const MlpDev& M;
+  const JtFactors& G;
+  const int32_t* offset;
+  int R;
+  float* g_xyz;
+  const float* rec;
+  int start, ccap, cap;
+  unsigned* bad;
+  int line_floats, rec_rows;
+  float* dbasis_slabs;
+  int wgs;
+  size_t lds;
+  hipStream_t st;
+};
+template <class C, bool DET, int RUN, int WAVES, int FLAGS>
+static void launch_scatter(const ScatterArgs& a) {
+  static bool attr = false;
+  if (!attr) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_shade_scatter<C, DET, RUN, WAVES, FLAGS>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBudget);
+    attr = true;
+  }
+  const long nbatch = ((long)a.ccap + 4 * RUN - 1) / (4 * RUN);
+  const int blocks = (int)std::min<long>((nbatch + WAVES - 1) / WAVES, (long)a.wgs);
+  hipLaunchKernelGGL((k_shade_scatter<C, DET, RUN, WAVES, FLAGS>), dim3(blocks), dim3(WAVES * 64), a.lds, a.st, a.D, a.M, a.G,
+                     a.offset, a.R, a.g_xyz, a.rec, a.start, a.ccap, a.cap, a.bad, a.line_floats, a.rec_rows, a.dbasis_slabs);
+}
+// the k_shade_scatter shapes that exist, per scene kind: a plan whose shape is not listed is JT_ERR_UNSUPPORTED
+struct ScatterShape {
+  bool det;
+  int run, waves, flags;
+  void (*launch)(const ScatterArgs&);
+};
+template <class C, bool DET, int RUN, int WAVES, int FLAGS>
+constexpr ScatterShape scatter_shape() { return {DET, RUN, WAVES, FLAGS, &launch_scatter<C, DET, RUN, WAVES, FLAGS>}; }
+template <class C>
+struct ScatterShapes;
+// VM-48: eight waves with runs of 8 / 16, and the twelve-wave shape
+template <>
+struct ScatterShapes<CfgBlender> {
+  typedef CfgBlender C;
+  static constexpr int N = 13;
+  static const ScatterShape* list() {
+    static const ScatterShape l[N] = {
+        scatter_shape<C, false, 8, 12, 3>(),
+        scatter_shape<C, false, 8, 8, 0>(),   scatter_shape<C, false, 8, 8, 1>(),   scatter_shape<C, false, 8, 8, 2>(),
+        scatter_shape<C, false, 8, 8, 3>(),   scatter_shape<C, true, 8, 8, 0>(),    scatter_shape<C, true, 8, 8, 2>(),
+        scatter_shape<C, false, 16, 8, 0>(),  scatter_shape<C, false, 16, 8, 1>(),  scatter_shape<C, false, 16, 8, 2>(),
+        scatter_shape<C, false, 16, 8, 3>(),  scatter_shape<C, true, 16, 8, 0>(),   scatter_shape<C, true, 16, 8, 2>()};
+    return l;
+  }
+};
+// 20 channels: eight or sixteen waves with runs of 8 / 16
+template <>
+struct ScatterShapes<CfgLlff> {
+  typedef CfgLlff C;
+  static constexpr int N = 24;
+  static const ScatterShape* list() {
+    static const ScatterShape l[N] = {
+        scatter_shape<C, false, 8, 8, 0>(),   scatter_shape<C, false, 8, 8, 1>(),   scatter_shape<C, false, 8, 8, 2>(),
+        scatter_shape<C, false, 8, 8, 3>(),   scatter_shape<C, true, 8, 8, 0>(),    scatter_shape<C, true, 8, 8, 2>(),
+        scatter_shape<C, false, 8, 16, 0>(),  scatter_shape<C, false, 8, 16, 1>(),  scatter_shape<C, false, 8, 16, 2>(),
+        scatter_shape<C, false, 8, 16, 3>(),  scatter_shape<C, true, 8, 16, 0>(),   scatter_shape<C, true, 8, 16, 2>(),
+        scatter_shape<C, false, 16, 8, 0>(),  scatter_shape<C, false, 16, 8, 1>(),  scatter_shape<C, false, 16, 8, 2>(),
+        scatter_shape<C, false, 16, 8, 3>(),  scatter_shape<C, true, 16, 8, 0>(),   scatter_shape<C, true, 16, 8, 2>(),
+        scatter_shape<C, false, 16, 16, 0>(), scatter_shape<C, false, 16, 16, 1>(), scatter_shape<C, false, 16, 16, 2>(),
+        scatter_shape<C, false, 16, 16, 3>(), scatter_shape<C, true, 16, 16, 0>(),  scatter_shape<C, true, 16, 16, 2>()};
+    return l;
+  }
+};
+template <class C>
+static const ScatterShape* find_scatter(const ShadeBwdPlan& P) {
+  const ScatterShape* l = ScatterShapes<C>::list();
+  for (int i = 0; i < ScatterShapes<C>::N; ++i)
+    if (l[i].det == P.sc_det && l[i].run == P.sc_run && l[i].waves == P.sc_waves && l[i].flags == P.sc_flags) return l + i;
+  return nullptr;
+}
+
+template <class C, bool B16, class... Args>
+static void launch_pose_gather(int blocks, hipStream_t st, Args... args) {
+  hipLaunchKernelGGL((k_pose_gather<C, B16>), dim3(blocks), dim3(256), 0, st, args...);
+}
+
+template <bool B16, int MT, int NT, int XF, int XA, class... Args>
+static void launch_wgrad_gemm(hipStream_t st, Args... args) {
+  if constexpr (B16) hipLaunchKernelGGL((k_wgrad_b16<MT, NT, XF, XA>), dim3(kWgradBlocks), dim3(256), 0, st, args...);
+  else hipLaunchKernelGGL((k_wgrad<MT, NT, XF, XA>), dim3(kWgradBlocks), dim3(256), 0, st, args...);
+}
+// the weight-gradient GEMMs of one chunk: dW3/db3 = GO^T MID ; dW2/db2 = G2^T H1 ; dW1/db1 = G1^T X(F, d) ; dBasis = GF^T PROD
+// (the last one only where dBasis does not come out of the scatter)
+template <class C, bool B16>
+static int launch_wgrad(const ShadeBwdPlan& P, const MlpDev& M, const PeMask& pm, const float* rec, const int32_t* offset,
+                        int R, int cap, int start, int ccap, float* slabs, hipStream_t st) {
+  typedef BwdCfg<C> B;
+  typedef WgradDims<C> W;
+  constexpr int XF1 = (C::KIND == JT_MLP_FEA) ? 1 : 2;
+  const int nb = kWgradBlocks, RR = P.rec_rows;
+  const G2Src gs = {M.w3, B::R_GO, B::R_MASK + 2, C::IN3, (C::KIND == JT_MLP_FEA) ? 0 : 12};
+  float* s3 = slabs;
+  float* s2 = s3 + W::P3 * nb;
+  float* s1 = s2 + W::P2 * nb;
+  float* sb = s1 + W::P1 * nb;
+  launch_wgrad_gemm<B16, 1, W::NT3, 0, 0>(st, rec, B::R_GO, 3, B::R_MID, C::IN3, B::R_F, B::R_VD, RR, pm, C::APP, offset, R,
+                                          cap, start, ccap, s3, gs);
+  JT_LAUNCH_CHECK();
+  if (P.lean)
+    launch_wgrad_gemm<B16, C::MT, C::MT, 0, 1>(st, rec, B::R_G2, C::HID, B::R_H1, C::HID, B::R_F, B::R_VD, RR, pm, C::APP,
+                                               offset, R, cap, start, ccap, s2, gs);
+  else
+    launch_wgrad_gemm<B16, C::MT, C::MT, 0, 0>(st, rec, B::R_G2, C::HID, B::R_H1, C::HID, B::R_F, B::R_VD, RR, pm, C::APP,
+                                               offset, R, cap, start, ccap, s2, gs);
+  JT_LAUNCH_CHECK();
+  launch_wgrad_gemm<B16, C::MT, W::NT1, XF1, 0>(st, rec, B::R_G1, C::HID, B::R_F, C::IN1, B::R_F, B::R_VD, RR, pm, C::APP,
+                                                offset, R, cap, start, ccap, s1, gs);
+  JT_LAUNCH_CHECK();
+  if (P.gemm_count == 4) {
+    launch_wgrad_gemm<B16, 1, W::NTB, 0, 0>(st, rec, B::R_GF, C::APP, B::R_PROD, C::NC, B::R_F, B::R_VD, RR, pm, C::APP,
+                                            offset, R, cap, start, ccap, sb, gs);
+    JT_LAUNCH_CHECK();
+  }
+  return JT_OK;
+}
+
+// executes plan_shade_bwd's plan: per chunk the per-sample backward on the main stream, its weight-gradient GEMMs on the
+// auxiliary stream
+template <class C>
+static int launch_shade_bwd(const ShadeBwdPlan& P, const Knobs& k, const Dev& D, const MlpDev& M, const PeMask& pm,
+                            const JtFactors& G, const JtMlp& GM, const int32_t* offset, int R, const float* rgb_s,
+                            const float* g_rgb_s, float* g_xyz, int cap, float* ws, size_t ws_bytes, hipStream_t st,
+                            hipStream_t aux, hipEvent_t ev_fork, hipEvent_t ev_join) {
+  typedef BwdCfg<C> B;
+  typedef WgradDims<C> WD;
+  if (P.status) return P.status;
+  const WsLayout<C> W(k);
+  if (ws_bytes < W.bytes(cap)) return JT_ERR_ARG;
+  const ScatterShape* scatter = nullptr;
+  if (P.second == kSecondScatter && !(scatter = find_scatter<C>(P))) return JT_ERR_UNSUPPORTED;
+  const int chunk = W.chunk;
+  const int nchunks = (int)(((long)cap + chunk - 1) / chunk);
+  float* recs = ws;
+  float* slabs = ws + W.rec_floats(cap);
+  const size_t cstride = W.slab_floats_per_chunk();
+  float* dbasis_slabs = slabs + (WD::P3 + WD::P2 + WD::P1) * kWgradBlocks;
+  const bool use_aux = P.gemm_forked, det = (P.ablate & 16) != 0;
+  hipStream_t ws_st = use_aux ? aux : st;
+  const int RR = P.rec_rows, ablate = P.ablate;
+  unsigned* bad = jt::fixed_bad_flag();
+  if (!bad) return JT_ERR_ARG;
+  const TileWs TW = tile_ws_carve(reinterpret_cast<char*>(ws) + W.main_bytes(cap), cap, chunk);
+  auto launch_bwd = [&](int ci) -> int {
     const int start = ci * chunk, ccap = std::min(chunk, cap - start);
-    const float* rc = recs + W::rec_floats_per_chunk() * ci;
-    if (pose_only) {
-      const long tiles = ((long)ccap + 31) / 32;
-      const int pblocks = (int)std::min<long>((tiles + 3) / 4, 2048L);
-      // (the 20-channel scene keeps the fp32 product: its bf16 instantiation needs 168 registers + 8 bytes of scratch at three
-      //  waves per SIMD, for a product that is a third of VM-48's)
-      if ((bf16x3_mode() & 4) && C::CA >= 48)
-        hipLaunchKernelGGL((k_pose_gather<C, (C::CA >= 48)>), dim3(pblocks), dim3(256), 0, st, D, M, offset, R, g_xyz, rc, start, ccap, cap, RR);
-      else
-        hipLaunchKernelGGL((k_pose_gather<C, false>), dim3(pblocks), dim3(256), 0, st, D, M, offset, R, g_xyz, rc, start, ccap, cap, RR);
-      JT_LAUNCH_CHECK();
-      return JT_OK;
+    long tiles = ((long)ccap + 31) / 32;
+    int blocks = (int)std::min<long>((tiles + B::NWAVE - 1) / B::NWAVE, chip().cus);   // one workgroup per CU (its LDS fills it)
+    float* rc = recs + W.rec_floats_per_chunk() * ci;
+    const size_t lds = (size_t)P.chain_lds;
+    switch (P.chain) {
+      case kChainSplitB16:
+        launch_chain<C, false, true, true>(blocks, lds, st, D, M, pm, G, offset, R, rgb_s, g_rgb_s, g_xyz, rc, start, ccap, cap,
+                                           ablate, bad, RR);
+        break;
+      case kChainSplit:
+        launch_chain<C, false, true, false>(blocks, lds, st, D, M, pm, G, offset, R, rgb_s, g_rgb_s, g_xyz, rc, start, ccap, cap,
+                                            ablate, bad, RR);
+        break;
+      case kChainFusedDet:
+        launch_chain<C, true, false, false>(blocks, lds, st, D, M, pm, G, offset, R, rgb_s, g_rgb_s, g_xyz, rc, start, ccap, cap,
+                                            ablate, bad, RR);
+        break;
+      default:
+        launch_chain<C, false, false, false>(blocks, lds, st, D, M, pm, G, offset, R, rgb_s, g_rgb_s, g_xyz, rc, start, ccap, cap,
+                                             ablate, bad, RR);
     }
-    if (tile) {
-      int rc_ = TS::template launch<1>(D, M, G, TW, offset, R, g_xyz, rc, start, ccap, cap, tile_line_len, st);
-      if (rc_) return rc_;
-      JT_LAUNCH_CHECK();
-      return JT_OK;
-    }
-    const size_t lds_s = scatter_lds(split, sflags, sw);
-#define JT_SCATTER_LAUNCH(RUN_, DET_, FL_, SW_)                                                                         \
-  {                                                                                                                     \
-    static bool attr = false;                                                                                           \
-    if (!attr) {                                                                                                        \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_shade_scatter<C, DET_, RUN_, SW_, FL_>),                \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                                \
-      attr = true;                                                                                                      \
-    }                                                                                                                   \
-    const long nbatch = ((long)ccap + 4 * RUN_ - 1) / (4 * RUN_);                                                       \
-    const int sblocks = (int)std::min<long>((nbatch + SW_ - 1) / SW_, (long)scatter_wgs(use_aux && C::CA >= 48, dbs, w12));                             \
-    hipLaunchKernelGGL((k_shade_scatter<C, DET_, RUN_, SW_, FL_>), dim3(sblocks), dim3(SW_ * 64), lds_s, st, D, M, G,   \
-                       offset, R, g_xyz, rc, start, ccap, cap, bad, line_floats, RR,                                    \
-                       slabs + (size_t)ci * cstride + (W::P3 + W::P2 + W::P1) * nb);                                    \
-  }
-#define JT_SCATTER_FL(RUN_, SW_)                                                                \
-  {                                                                                             \
-    if (det && dbs) JT_SCATTER_LAUNCH(RUN_, true, 2, SW_)                                       \
-    else if (det) JT_SCATTER_LAUNCH(RUN_, true, 0, SW_)                                         \
-    else if (sflags == 1 && dbs) JT_SCATTER_LAUNCH(RUN_, false, 3, SW_)                         \
-    else if (sflags == 1) JT_SCATTER_LAUNCH(RUN_, false, 1, SW_)                                \
-    else if (dbs) JT_SCATTER_LAUNCH(RUN_, false, 2, SW_)                                        \
-    else JT_SCATTER_LAUNCH(RUN_, false, 0, SW_)                                                 \
-  }
-#define JT_SCATTER_RUN(RUN_)                                                                    \
-  {                                                                                             \
-    if (C::CA < 48 && sw == 16) JT_SCATTER_FL(RUN_, (C::CA < 48 ? 16 : 8))                      \
-    else JT_SCATTER_FL(RUN_, 8)                                                                 \
-  }
-    // (experiment, JT_SCATTER_WAVES=12 with JT_BWD_SPLIT=8: three waves per SIMD for the 48-channel scatter)
-    if (w12)
-      JT_SCATTER_LAUNCH(8, false, 3, (C::CA >= 48 ? 12 : 8))
-    else if (split == 8) JT_SCATTER_RUN(8) else JT_SCATTER_RUN(16)
-#undef JT_SCATTER_RUN
-#undef JT_SCATTER_FL
-#undef JT_SCATTER_LAUNCH
     JT_LAUNCH_CHECK();
     return JT_OK;
   };
-  auto launch_wgrad = [&](int ci) -> int {
+  auto launch_second = [&](int ci) -> int {
+    if (P.second == kSecondNone) return JT_OK;
     const int start = ci * chunk, ccap = std::min(chunk, cap - start);
-    const float* rec = recs + W::rec_floats_per_chunk() * ci;
-    // dW3/db3 = GO^T MID ; dW2/db2 = G2^T H1 ; dW1/db1 = G1^T X(F, d) ; dBasis = GF^T PROD
-    const G2Src gs = {M.w3, B::R_GO, B::R_MASK + 2, C::IN3, (C::KIND == JT_MLP_FEA) ? 0 : 12};
-    float* s3 = slabs + (size_t)ci * cstride;
-    float* s2 = s3 + W::P3 * nb;
-    float* s1 = s2 + W::P2 * nb;
-    float* sb = s1 + W::P1 * nb;
-#define JT_WGRAD_LAUNCH(KERNEL)                                                                                          \
-  hipLaunchKernelGGL((KERNEL<1, NT3, 0>), dim3(nb), dim3(256), 0, ws_st, rec, B::R_GO, 3, B::R_MID, C::IN3, B::R_F,      \
-                     B::R_VD, RR, pm, C::APP, offset, R, cap, start, ccap, s3, gs);                                      \
-  JT_LAUNCH_CHECK();                                                                                                     \
-  if (lean) {                                                                                                            \
-  hipLaunchKernelGGL((KERNEL<C::MT, C::MT, 0, 1>), dim3(nb), dim3(256), 0, ws_st, rec, B::R_G2, C::HID, B::R_H1, C::HID, \
-                     B::R_F, B::R_VD, RR, pm, C::APP, offset, R, cap, start, ccap, s2, gs);                              \
-  } else {                                                                                                               \
-  hipLaunchKernelGGL((KERNEL<C::MT, C::MT, 0>), dim3(nb), dim3(256), 0, ws_st, rec, B::R_G2, C::HID, B::R_H1, C::HID,    \
-                     B::R_F, B::R_VD, RR, pm, C::APP, offset, R, cap, start, ccap, s2, gs);                              \
-  }                                                                                                                      \
-  JT_LAUNCH_CHECK();                                                                                                     \
-  hipLaunchKernelGGL((KERNEL<C::MT, NT1, XF1>), dim3(nb), dim3(256), 0, ws_st, rec, B::R_G1, C::HID, B::R_F, C::IN1,     \
-                     B::R_F, B::R_VD, RR, pm, C::APP, offset, R, cap, start, ccap, s1, gs);                              \
-  JT_LAUNCH_CHECK();                                                                                                     \
-  if (!dbs) {                                                                                                            \
-  hipLaunchKernelGGL((KERNEL<1, NTB, 0>), dim3(nb), dim3(256), 0, ws_st, rec, B::R_GF, C::APP, B::R_PROD, C::NC, B::R_F, \
-                     B::R_VD, RR, pm, C::APP, offset, R, cap, start, ccap, sb, gs);                                      \
-  JT_LAUNCH_CHECK();                                                                                                     \
-  }
-    if (bf16x3_mode() & 2) {
-      JT_WGRAD_LAUNCH(k_wgrad_b16)
+    const float* rc = recs + W.rec_floats_per_chunk() * ci;
+    if (P.second == kSecondPoseGather || P.second == kSecondPoseGatherB16) {
+      const long tiles = ((long)ccap + 31) / 32;
+      const int pblocks = (int)std::min<long>((tiles + 3) / 4, 2048L);
+      if (P.second == kSecondPoseGatherB16)
+        launch_pose_gather<C, (C::CA >= 48)>(pblocks, st, D, M, offset, R, g_xyz, rc, start, ccap, cap, RR);
+      else
+        launch_pose_gather<C, false>(pblocks, st, D, M, offset, R, g_xyz, rc, start, ccap, cap, RR);
+    } else if (P.second == kSecondTile) {
+      int rc_ = TileSel<C>::template launch<1>(D, M, G, TW, offset, R, g_xyz, rc, start, ccap, cap, P.tile_line_len, P.tile_wgs,
+                                               P.tile_ratio, st);
+      if (rc_) return rc_;
     } else {
-      JT_WGRAD_LAUNCH(k_wgrad)
+      const ScatterArgs a = {D, M, G, offset, R, g_xyz, rc, start, ccap, cap, bad, P.line_floats, RR,
+                             dbasis_slabs + (size_t)ci * cstride, P.sc_wgs, (size_t)P.sc_lds, st};
+      scatter->launch(a);
     }
-#undef JT_WGRAD_LAUNCH
+    JT_LAUNCH_CHECK();
     return JT_OK;
   };
-  // (JT_SCATTER_FIRST=1: the scatter in front of the fork, as in the fused kernel's order)
-  static const bool scatter_first = [] { const char* e = getenv("JT_SCATTER_FIRST"); return e && atoi(e) != 0; }();
+  auto launch_gemms = [&](int ci) -> int {
+    const int start = ci * chunk, ccap = std::min(chunk, cap - start);
+    const float* rec = recs + W.rec_floats_per_chunk() * ci;
+    float* s = slabs + (size_t)ci * cstride;
+    return P.gemm_b16 ? launch_wgrad<C, true>(P, M, pm, rec, offset, R, cap, start, ccap, s, ws_st)
+                      : launch_wgrad<C, false>(P, M, pm, rec, offset, R, cap, start, ccap, s, ws_st);
+  };
+  const bool pipe = P.gemm_pipe;
   for (int ci = 0; ci < nchunks; ++ci) {
     int rc = launch_bwd(ci);
     if (rc) return rc;
-    if (scatter_first && (rc = launch_scatter(ci))) return rc;
+    if (P.scatter_first && (rc = launch_second(ci))) return rc;
     if (use_aux && pipe) {
       if (hipEventRecord(ev_fork, st) != hipSuccess) return JT_ERR_ARG;
       if (hipStreamWaitEvent(aux, ev_fork, 0) != hipSuccess) return JT_ERR_ARG;
-      if ((rc = launch_wgrad(ci))) return rc;
+      if ((rc = launch_gemms(ci))) return rc;
     }
-    if (!scatter_first && (rc = launch_scatter(ci))) return rc;
+    if (!P.scatter_first && (rc = launch_second(ci))) return rc;
   }
-  if (dbs && !(ablate & 1)) {
+  if (P.dbasis_in_scatter && P.second == kSecondScatter) {
     // dBasis: the sum of the scatter workgroups' slabs, on the launch stream behind the last scatter
     const int ry = det ? 1 : 8;
-    hipLaunchKernelGGL((k_dbasis_reduce<C>), dim3((ScatCfg<C>::DB_SLAB + 255) / 256, ry), dim3(256), 0, st,
-                       slabs + (W::P3 + W::P2 + W::P1) * nb, cstride, chunk, scatter_wgs(use_aux && C::CA >= 48, dbs, w12), 4 * split,
-                       sw, offset, R, cap, GM.basis);
+    hipLaunchKernelGGL((k_dbasis_reduce<C>), dim3((ScatCfg<C>::DB_SLAB + 255) / 256, ry), dim3(256), 0, st, dbasis_slabs, cstride,
+                       chunk, P.sc_wgs, 4 * P.sc_run, P.sc_waves, offset, R, cap, GM.basis);
     JT_LAUNCH_CHECK();
   }
-  if (ablate & 4) return JT_OK;
+  if (P.gemm_count == 0) return JT_OK;
   if (use_aux && !pipe) {
     if (hipEventRecord(ev_fork, st) != hipSuccess) return JT_ERR_ARG;
     if (hipStreamWaitEvent(aux, ev_fork, 0) != hipSuccess) return JT_ERR_ARG;
@@ -2336,22 +2435,52 @@ static int launch_shade_bwd(const Dev& D, const MlpDev& M, const PeMask& pm, con
   if (!use_aux && ev_fork && hipEventRecord(ev_fork, st) != hipSuccess) return JT_ERR_ARG;
   if (!(use_aux && pipe)) {
     for (int ci = 0; ci < nchunks; ++ci) {
-      int rc = launch_wgrad(ci);
+      int rc = launch_gemms(ci);
       if (rc) return rc;
     }
   }
   {
     const int ry = det ? 1 : 32;  // slab groups that add into dW atomically; ONE group = a fixed summation order
     // (dBasis out of the scatter: the last range of the reduce kernel's grid, the dBasis GEMM's slabs, is left off)
-    const int nblk = (int)((W::P3 + 255) / 256 + (W::P2 + 255) / 256 + (W::P1 + 255) / 256 + (dbs ? 0 : (W::PB + 255) / 256));
+    const int nblk = (int)((WD::P3 + 255) / 256 + (WD::P2 + 255) / 256 + (WD::P1 + 255) / 256 +
+                           (P.dbasis_in_scatter ? 0 : (WD::PB + 255) / 256));
     const MlpGrad gm = {GM.basis, GM.w1, GM.b1, GM.w2, GM.b2, GM.w3, GM.b3};
-    hipLaunchKernelGGL((k_wgrad_reduce4<C>), dim3(nblk, ry), dim3(256), 0, ws_st, slabs, nb, cstride, chunk, offset, R, cap,
-                       gm);
+    hipLaunchKernelGGL((k_wgrad_reduce4<C>), dim3(nblk, ry), dim3(256), 0, ws_st, slabs, kWgradBlocks, cstride, chunk, offset, R,
+                       cap, gm);
     JT_LAUNCH_CHECK();
   }
   if (ws_st != st) {
     if (hipEventRecord(ev_join, aux) != hipSuccess) return JT_ERR_ARG;
   }
+  return JT_OK;
+}
+
+// the plan's inputs as a scene and a call give them
+static ShadeBwdInputs shade_bwd_inputs(const JtScene* s, bool want_factor_grads, bool want_mlp_grads, int flags, bool have_aux) {
+  ShadeBwdInputs in = {};
+  for (int a = 0; a < 3; ++a) in.line_len[a] = s->line_len[a], in.plane_h[a] = s->plane_h[a], in.plane_w[a] = s->plane_w[a];
+  in.det = jt_deterministic() != 0;
+  in.want_factor_grads = want_factor_grads, in.want_mlp_grads = want_mlp_grads;
+  in.flags = flags, in.have_aux = have_aux;
+  return in;
+}
+
+// The plan jt_shade_backward would execute for this scene under the library's current modes (jt_render.h has the indices);
+// needs no device memory and no stream
+extern "C" int jt_shade_backward_plan(const JtScene* scene, int want_factor_grads, int want_mlp_grads, int flags, int have_aux,
+                                      int32_t* out16) {
+  const int kind = shade_kind(scene);
+  if (kind < 0 || !out16) return JT_ERR_UNSUPPORTED;
+  for (int a = 0; a < 3; ++a)
+    if (scene->plane_h[a] < 1 || scene->plane_w[a] < 1 || scene->line_len[a] < 1) return JT_ERR_ARG;
+  const ShadeBwdInputs in = shade_bwd_inputs(scene, want_factor_grads != 0, want_mlp_grads != 0, flags, have_aux != 0);
+  const ShadeBwdPlan P = kind == 0 ? plan_shade_bwd<CfgBlender>(knobs(), chip(), in) : plan_shade_bwd<CfgLlff>(knobs(), chip(), in);
+  if (P.status) return P.status;
+  if (P.second == kSecondScatter && !(kind == 0 ? find_scatter<CfgBlender>(P) : find_scatter<CfgLlff>(P)))
+    return JT_ERR_UNSUPPORTED;
+  const int32_t v[16] = {P.split_requested, P.split, P.chain, P.second, P.sc_det, P.sc_run, P.sc_waves, P.sc_flags,
+                         P.sc_lds, P.sc_wgs, P.lean, P.rec_rows, P.dbasis_in_scatter, P.gemm_b16, P.gemm_count, P.gemm_forked};
+  for (int i = 0; i < 16; ++i) out16[i] = v[i];
   return JT_OK;
 }
 
@@ -2376,7 +2505,6 @@ extern "C" int jt_shade_backward(const JtScene* scene, const JtFactors* factors,
     if (g_factors && (!g_factors->app_plane[a] || !g_factors->app_line[a])) return JT_ERR_ARG;
   JtFactors no_fac = {};
   JtMlp no_mlp = {};
-  if (!g_mlp) flags |= JT_SHADE_SKIP_WGRAD | kNoGradRecords;  // nobody will read the gradient records
   const JtFactors& GFr = g_factors ? *g_factors : no_fac;
   const JtMlp& GMr = g_mlp ? *g_mlp : no_mlp;
   if (D.ndc && !zvals) return JT_ERR_ARG;
@@ -2387,12 +2515,14 @@ extern "C" int jt_shade_backward(const JtScene* scene, const JtFactors* factors,
   MlpDev M = {mlp->basis, mlp->w1, mlp->b1, mlp->w2, mlp->b2, mlp->w3, mlp->b3};
   PeMask pm = pe_masks(scene->fea_pe_progress, scene->view_pe_progress, scene->fea_pe, scene->view_pe);
   hipStream_t st = (hipStream_t)stream;
+  const Knobs k = knobs();
+  const ShadeBwdInputs in = shade_bwd_inputs(scene, g_factors != nullptr, g_mlp != nullptr, flags,
+                                             aux_stream && ev_fork && ev_join);
   if (kind == 0)
-    return launch_shade_bwd<CfgBlender>(D, M, pm, GFr, GMr, shade_offset, n_rays, rgb_s, g_rgb_s, g_xyz_app,
-                                        n_entries_max, (float*)workspace, workspace_bytes, flags, st, (hipStream_t)aux_stream,
-                                        (hipEvent_t)ev_fork, (hipEvent_t)ev_join);
-  return launch_shade_bwd<CfgLlff>(D, M, pm, GFr, GMr, shade_offset, n_rays, rgb_s, g_rgb_s, g_xyz_app,
-                                   n_entries_max,
-                                   (float*)workspace, workspace_bytes, flags, st, (hipStream_t)aux_stream,
-                                   (hipEvent_t)ev_fork, (hipEvent_t)ev_join);
+    return launch_shade_bwd<CfgBlender>(plan_shade_bwd<CfgBlender>(k, chip(), in), k, D, M, pm, GFr, GMr, shade_offset, n_rays,
+                                        rgb_s, g_rgb_s, g_xyz_app, n_entries_max, (float*)workspace, workspace_bytes, st,
+                                        (hipStream_t)aux_stream, (hipEvent_t)ev_fork, (hipEvent_t)ev_join);
+  return launch_shade_bwd<CfgLlff>(plan_shade_bwd<CfgLlff>(k, chip(), in), k, D, M, pm, GFr, GMr, shade_offset, n_rays, rgb_s,
+                                   g_rgb_s, g_xyz_app, n_entries_max, (float*)workspace, workspace_bytes, st,
+                                   (hipStream_t)aux_stream, (hipEvent_t)ev_fork, (hipEvent_t)ev_join);
 }

@@ -194,19 +194,19 @@ _AUX_ENV = os.environ.get("JT_NO_AUX")
 USE_AUX_STREAM = _AUX_ENV != "1"
 
 
-def _use_aux(cfg):
+def _use_aux(scene):
     """The weight-gradient GEMMs on the auxiliary stream?  Where the appearance backward runs SPLIT (chain kernel, then the
     atomic-bound scatter) they fork behind the chain and run beside the scatter: 3.12 -> 3.07 ms on VM-48 (round 5), 0.09 ms
     on the 20-channel scene (round 4).  Beside the FUSED kernel -- VM-48 with the fp32 chain, jt_shade_set_bwd_split(0) -- they
-    cost 0.06-0.10 ms (their registers and the persistent walk keep each other off the CUs) and stay on the launch stream."""
+    cost 0.06-0.10 ms (their registers and the persistent walk keep each other off the CUs) and stay on the launch stream.
+    Which of the two it is the library says (jt_shade_backward_plan out[0]: the split mode with the default resolved)."""
     if not USE_AUX_STREAM:
         return False
     if _AUX_ENV == "0":
         return True
-    split = lib.jt_shade_bwd_split()
-    if split < 0:
-        return cfg.n_comp_app < 48 or bool(lib.jt_shade_matrix_mode() & 4)
-    return split != 0
+    plan = (ctypes.c_int32 * 16)()
+    check(lib.jt_shade_backward_plan(scene, 1, 1, 0, 1, plan), "jt_shade_backward_plan")
+    return plan[0] != 0
 
 
 def _aux_stream(dev):
@@ -720,7 +720,8 @@ class RenderRays(torch.autograd.Function):
                                        ptr(torch.empty_like(rgb_s)), cap, ptr(ws), nbytes,
                                        _lib.JT_SHADE_POSE_ONLY if ctx.pose_only else 0, st),
                   "jt_shade_forward")
-        if _use_aux(cfg) and want_mlp:
+        use_aux = _use_aux(scene)
+        if use_aux and want_mlp:
             aux, ev_fork, ev_join = _aux_stream(dev)
             # the weight-gradient GEMMs read mlp_t / ws and write g_mlp on the auxiliary stream
             if not torch.cuda.is_current_stream_capturing():  # graph-pool memory is never recycled elsewhere
@@ -759,7 +760,7 @@ class RenderRays(torch.autograd.Function):
             t_bwd_end.record()
         if dp:
             reducer.reduce(2, 3)  # appearance planes + lines are final
-        elif (ADAM_EARLY and want_fac and not det and _use_aux(cfg) and (reg_first or ctx.reg is None or g_reg is None)
+        elif (ADAM_EARLY and want_fac and not det and use_aux and (reg_first or ctx.reg is None or g_reg is None)
               and not torch.cuda.is_current_stream_capturing()):
             # the appearance factors' gradients are final HERE (their regulariser part was written before the render backward);
             # what follows on this stream -- the density backward -- is bound by the float-atomic path and leaves the memory

@@ -146,6 +146,14 @@ def _check_pose(tag, kind, grid, aabb, o, d, S, cd=16, variant="mfma", det=False
         assert _ran(seen, k), (tag, "expected", k, seen)
     for k in absent:
         assert not _ran(seen, k), (tag, "unexpected", k, seen)
+    # what the plan queries say this backward launches (tests/test_launch_plan.py checks them on the CPU) is what ran
+    # (the appearance kernels are only required where a sample was shaded)
+    from joint_tensorf_amd import ops
+    from tests.test_launch_plan import missing_from, planned_kernels
+    shade, march, _, _ = planned_kernels(kind, grid, S, o.shape[0], cd=cd, variant=variant, det=det, pose=True,
+                                         stored=ops.POSE_MARCH_DERIVATIVES)
+    planned = march + (shade if cen["shaded"] else [])
+    assert not missing_from(planned, hip["kernels"]), (tag, planned, seen)
     assert hip["grads"] is None and hip["param_grads"] == 0, (tag, "a parameter received a gradient")
     assert not hip["overruns"], (tag, "a kernel wrote past its buffer (shape, bytes changed)", hip["overruns"])
     assert ref["relu"].get("max_abs", 0.0) <= 2e-5, ref["relu"]   # ReLU signs decided differently: near-ties only

@@ -24,7 +24,8 @@ when two workgroups fit (2 (b + 256) <= 163 840, b <= 81 664).  Cd 16, n = 1 000
   doubles 8w  47 008 + 128 L <= 81 664   <=> L <= 270     doubles 16w 90 016 + 128 L <= 161 792 <=> L <= 560
   floats 16w  90 016 +  64 L <= 161 792  <=> L <= 1 121   (floats 8w: 47 008 + 64 L <= 81 664 <=> L <= 541, never first)
   floats 16w without the prefix table: 86 016 + 64 L <= 161 792 <=> L <= 1 184;  then no LDS line, 8 waves.
-  The prefix table is a runtime argument, not part of the kernel's name: rows 1 122 and 1 184 rest on this arithmetic.
+  The prefix table is a runtime argument, not part of the kernel's name: rows 1 122 and 1 184 rest on this arithmetic
+  (and on jt_march_backward_plan's prefix field, which tests/test_launch_plan.py holds to the row ids without a GPU).
   At L = 24: 16 384 rays keep the table (doubles, 16 waves: 86 016 + 3 072 + 65 536 <= 161 792); 16 385 rays have none
   and take doubles at eight waves (2 (46 080 + 256) <= 163 840).
   Cd 8: L = 24 doubles 8w; L = 1 185 floats 16w (doubles 16w: 86 016 + 75 840 > 161 792; floats 8w: 2 x 85 184 > 163 840).
@@ -139,6 +140,11 @@ def _check_row(tag, kind, grid, aabb, o, d, S, cd=16, variant="mfma", det=False,
     assert hip["kernels"], "the profiler reported no device kernels"
     for k in expect:
         assert any(k in n for n in seen), (tag, k, seen)
+    # what the plan queries say this backward launches (tests/test_launch_plan.py checks them on the CPU) is what ran
+    from tests.test_launch_plan import missing_from, planned_kernels
+    shade, march, _, _ = planned_kernels(kind, grid, S, o.shape[0], cd=cd, variant=variant, det=det)
+    planned = march + (shade if int(hip["shade_mask"].sum()) else [])
+    assert not missing_from(planned, hip["kernels"]), (tag, planned, sorted(hip["kernels"]))
     rep = ref["relu"]
     assert rep.get("max_abs", 0.0) <= 2e-5, rep   # ReLU signs the fp64 reference decides differently: near-ties only
     for key, tol in (("rgb", TOL_VAL), ("opacity", TOL_VAL), ("depth", TOL_DEPTH)):
