@@ -9,6 +9,8 @@ a logical [1,C,H,W] parameter without a copy when the parameter already lives ch
 import ctypes
 import math
 import os
+from collections import namedtuple
+from typing import NamedTuple
 
 import torch
 
@@ -258,8 +260,8 @@ def _reg_scratch(dev):
     return _REG_SCRATCH[key]
 
 
-# value + gradient of the regularisers in one launch at forward time (RenderRays; JT_FUSE_REG=0 turns it off)
-FUSE_REG_GRADIENT = os.environ.get("JT_FUSE_REG", "1") != "0"
+# value + gradient of the regularisers in one launch at forward time (RenderRays, where the caller gives cfg.reg_weights): how
+# often the backward found the forward's gradient right / had to overwrite it
 REG_FUSION_STATS = {"trusted": 0, "rewritten": 0}
 
 
@@ -464,6 +466,139 @@ def _mlp_struct(basis, w1, b1, w2, b2, w3, b3):
 # ----------------------------------------------------------------------------------------------
 # the renderer
 # ----------------------------------------------------------------------------------------------
+# What one render does is decided ONCE per forward and once per backward, by two pure functions of plain flags
+# (plan_render_forward / plan_render_backward: no torch, no library, no globals -- tests/test_render_plan.py walks every
+# combination on the CPU); RenderRays.forward / .backward gather the flags, plan, and then execute top to bottom.
+def _reg_covered(tv_app):
+    """the gradient groups (density planes, density lines, appearance planes, ...) of which the regularisers' gradient writes
+    EVERY element -- L1 on the density factors, TV on the colours: they need no zero fill in front of it"""
+    return (0, 1, 2) if tv_app else (0, 1)
+
+
+class ForwardPlan(NamedTuple):
+    recording: bool    # a backward can follow: the shade forward leaves its records in the workspace
+    pose_only: bool    # ... and only the rays want a gradient: the light set of records
+    keep_dfeat: bool   # jt_march_forward_pose: the march also stores d(density feature) / d(coordinates) for the backward
+    sync_sizing: bool  # one host read of the shaded count sizes everything that is per shaded sample
+    timed: bool        # the "fwd" pair of the step timers
+    reg: str           # the regularisers: None, "value" (jt_reg_losses_forward) or "fused" (value AND gradient, jt_reg_losses_fused)
+    reg_mlp: bool      # "fused": the gradient buffers made for it carry the basis / MLP group too
+    unzeroed: tuple    # "fused": the groups of those buffers that get no zero fill
+
+
+def plan_render_forward(grad_enabled, wants_any, wants_scene, wants_reg_factors, want_mlp, pose_march, det, oversize, capturing,
+                        timers_on, has_reg, has_hint, tv_app, dp_on):
+    """wants_*: which inputs want a gradient (any; any scene parameter; all of the density factors and appearance planes; any of
+    basis / MLP).  pose_march: POSE_MARCH_DERIVATIVES.  det: the library's deterministic mode.  oversize: the worst-case tape
+    is beyond TAPE_SYNC_ENTRIES.  has_reg / has_hint / tv_app: cfg.reg_flags is set / cfg.reg_weights is / TV on the colours.
+    dp_on: data-parallel collectives are on."""
+    recording = grad_enabled and wants_any
+    pose_only = recording and not wants_scene
+    # value + gradient in one launch: only where the backward will find dL/d reg3 to be the hint AND may use buffers made here
+    fused = has_reg and has_hint and wants_reg_factors and not dp_on and not det
+    return ForwardPlan(recording=recording, pose_only=pose_only, keep_dfeat=pose_only and pose_march and not det,
+                       sync_sizing=oversize and not capturing, timed=timers_on and recording,
+                       reg="fused" if fused else "value" if has_reg else None, reg_mlp=fused and want_mlp,
+                       unzeroed=_reg_covered(tv_app) if fused else ())
+
+
+class BackwardPlan(NamedTuple):
+    buffers: str       # the factor gradients: None, "forward" (made by the forward's fused regulariser launch), "fresh" or
+    #                    "shadow" (deterministic: fresh float buffers under an int64 fixed-point shadow)
+    groups: int        # "fresh" / "shadow": gradient groups in the one flat buffer (4 factor sets, + basis / MLP)
+    unzeroed: tuple    # "fresh": the groups that get no zero fill (the regularisers' gradient is written in its place)
+    reg_before: str    # the regularisers' gradient in front of the shade backward: None, "trusted" (the forward wrote it),
+    #                    "overwrite" (the forward wrote it for another dL/d reg3) or "write"; the render gradient lands on top
+    reg_after: bool    # ... or added behind the march backward (and the collectives, and the fixed-point conversion)
+    dp: bool           # the gradient groups are all-reduced as they become final
+    mlp: str           # basis / MLP gradients: None, "carved" (group 4 of the flat buffer) or "zeros" (a tensor each)
+    fork: bool         # the weight-gradient GEMMs on the auxiliary stream
+    early: bool        # the appearance gradients are offered to the optimizer behind the shade backward (take_early_grads)
+    march_pose: bool   # jt_march_backward_pose (reads the stored dfeat_dn) instead of jt_march_backward
+    timers: tuple      # the kinds of step-timer pairs around the shade backward, in the order they are appended
+    walk_timed: bool   # the "march_bwd" pair and its sample count
+
+
+def plan_render_backward(want_fac, want_mlp, det, dp_on, has_reg, tv_app, has_g_reg, hint_holds, pre, use_aux, adam_early,
+                         capturing, kept_dfeat, timers_on=False, timers_walk=False):
+    """want_fac / want_mlp: any factor / any of basis and MLP wants a gradient.  has_reg: the regularisers rode on this node;
+    has_g_reg: a gradient arrived for them; hint_holds: it is the one the forward was told (_reg_hint_holds).  pre: None, or the
+    want_mlp the forward made its gradient buffers for.  use_aux: _use_aux(scene).  kept_dfeat: the forward march stored
+    dfeat_dn.  Raises what the node refuses -- before anything of that backward is launched."""
+    fused = want_fac and want_mlp
+    reg_live = has_reg and has_g_reg
+    buffers, groups, unzeroed, reg_before = None, 0, (), None
+    if det and want_fac:
+        if dp_on:
+            raise RuntimeError("JT_DETERMINISTIC is a single-process debugging mode")
+        buffers, groups, fused = "shadow", 4, False
+    elif want_fac and pre is not None and pre == fused:
+        buffers, reg_before = "forward", "trusted" if hint_holds else "overwrite"
+    elif want_fac:
+        # single process with the regularisers in this node: their gradient is WRITTEN first, in place of the zero fill of the
+        # tensors it covers (before: fill + read-modify-write of the same bytes)
+        buffers, groups = "fresh", 5 if fused else 4
+        if reg_live and not dp_on:
+            reg_before, unzeroed = "write", _reg_covered(tv_app)
+    dp = dp_on and fused
+    if dp_on and not dp and (want_fac or want_mlp):
+        raise RuntimeError("data-parallel render backward needs the fused path with all scene gradients wanted")
+    if reg_live and not want_fac:
+        raise RuntimeError("regulariser gradient wanted without factor gradients")
+    fork = use_aux and want_mlp
+    timed = timers_on and (want_fac or want_mlp)   # (not for a pose-only backward)
+    return BackwardPlan(
+        buffers=buffers, groups=groups, unzeroed=unzeroed, reg_before=reg_before, reg_after=reg_live and reg_before is None,
+        dp=dp, mlp="carved" if fused else "zeros" if want_mlp else None, fork=fork,
+        # (their regulariser part must be in by then; the offer looks at use_aux, not at the fork: the optimizer steps on that stream)
+        early=(not dp and adam_early and want_fac and not det and use_aux and (reg_before is not None or not reg_live)
+               and not capturing),
+        march_pose=kept_dfeat and not want_fac,
+        timers=() if not timed else ("bwd_chain", "bwd_scatter", "bwd") if fork else ("bwd",),
+        walk_timed=timed and timers_walk)
+
+
+# What a render's forward leaves for its backward.  cap: capacity of the per-shaded-sample tensors; sdp .. sal: the factors'
+# channel-last storage; dfeat_dn: None unless the march kept it; ws_ticket: of the shade workspace, while this call's records are
+# the ones in it; reg: (hw[9], Cd, Ca, TV on the density, TV on the colours) as jt_reg_losses_* take them, or None; pre: (gradient
+# tensors by group, flat buffer, spans, hint, with basis / MLP) of a forward that ran the regularisers "fused", or None
+_Tape = namedtuple("_Tape", "cfg cap pose_only rays_o rays_d jitter zvals sdp sdl sap sal mlp_t sigma_feat weight tmin offset "
+                            "sidx eray esmp vdir rgb_s cmask dfeat_dn ws_ticket reg pre", defaults=(None, None))
+
+
+def march_bwd_counts_offset(R, S):
+    """byte offset of the per-ray listed-sample counts (int32 [R]) in jt_march_backward's workspace: behind gfeat [R,S] f32 and
+    vlist [R,S] u16, every block rounded up to 256 bytes (a restatement of jt_march.hip: march_bwd_ws_layout, held to
+    jt_march_backward_workspace_bytes by tests/test_render_plan.py)"""
+    o = (R * S * 4 + 255) // 256 * 256
+    return (o + R * S * 2 + 255) // 256 * 256
+
+
+def _timer_pair():
+    """(start, end) timing events, the start recorded on the current stream"""
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0.record()
+    return t0, t1
+
+
+def _shade_forward(scene, fac, mlp, t, rgb_s, ws, nbytes, st):
+    """jt_shade_forward over the tape's sample lists into rgb_s; ws: the record workspace (None: no records are left)"""
+    ws_args = (None, 0, 0) if ws is None else (ptr(ws), nbytes, _lib.JT_SHADE_POSE_ONLY if t.pose_only else 0)
+    check(lib.jt_shade_forward(scene, fac, mlp, ptr(t.rays_o), ptr(t.rays_d), ptr(t.jitter), ptr(t.zvals), ptr(t.tmin),
+                               ptr(t.offset), t.rays_o.shape[0], ptr(t.eray), ptr(t.esmp), ptr(t.vdir), ptr(rgb_s), t.cap,
+                               *ws_args, st), "jt_shade_forward")
+
+
+def _reg_backward(reg, fac, g_reg, gfac, accumulate, dev, st):
+    """jt_reg_losses_backward: the regularisers' gradient under dL/d reg3 = g_reg (None: zeros) written over (accumulate 0) or
+    added into (1) the factor gradients"""
+    hw, Cd, Ca, wd, wa = reg
+    g3 = torch.zeros(3, device=dev, dtype=torch.float32) if g_reg is None else g_reg.contiguous().float()
+    scratch = torch.empty(36, device=dev, dtype=torch.float32)
+    check(lib.jt_reg_losses_backward(fac, hw, Cd, Ca, ptr(g3), wd, wa, gfac, accumulate, ptr(scratch), st),
+          "jt_reg_losses_backward")
+
+
 class RenderRays(torch.autograd.Function):
     """(rays, VM factors, basis, MLP) -> rgb [R,3], depth [R], opacity [R].
 
@@ -471,21 +606,25 @@ class RenderRays(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, cfg, rays_o, rays_d, jitter, zvals, *params):
-        dp, dl, ap, al = params[0:3], params[3:6], params[6:9], params[9:12]
-        basis, w1, b1, w2, b2, w3, b3 = params[12:19]
         dev = rays_o.device
         assert dev.type == "cuda", "joint_tensorf_amd renders on the GPU only (no CPU fallback)"
         status_word(dev)  # bound to the library before any backward can want to report into it
         R, S = rays_o.shape[0], cfg.n_samples
+        nig = ctx.needs_input_grad
+        flags = getattr(cfg, "reg_flags", None)    # (with_tv_density, with_tv_app): the regularisers of the same factors ride here
+        hint = getattr(cfg, "reg_weights", None)   # dL/d reg3 as this step's loss weights will make it, if the caller knows
+        plan = plan_render_forward(
+            grad_enabled=getattr(cfg, "grad_enabled", True), wants_any=any(nig), wants_scene=any(nig[5:]),
+            wants_reg_factors=all(nig[5:14]), want_mlp=any(nig[17:24]), pose_march=POSE_MARCH_DERIVATIVES,
+            det=bool(lib.jt_set_deterministic(-1)), oversize=R * S > TAPE_SYNC_ENTRIES,
+            capturing=torch.cuda.is_current_stream_capturing(), timers_on=STEP_TIMERS is not None, has_reg=flags is not None,
+            has_hint=hint is not None, tv_app=flags is not None and bool(flags[1]), dp_on=_DP["world"] > 1 or _DP["force"])
         rays_o = rays_o.detach().contiguous().float()
         rays_d = rays_d.detach().contiguous().float()
         jitter = None if jitter is None else jitter.detach().contiguous().float().view(-1)
         zvals = None if zvals is None else zvals.detach().contiguous().float().view(-1)
-        sdp = [factor_storage(p) for p in dp]
-        sdl = [factor_storage(p) for p in dl]
-        sap = [factor_storage(p) for p in ap]
-        sal = [factor_storage(p) for p in al]
-        mlp_t = [t.detach().contiguous() for t in (basis, w1, b1, w2, b2, w3, b3)]
+        sdp, sdl, sap, sal = ([factor_storage(p) for p in params[k:k + 3]] for k in (0, 3, 6, 9))
+        mlp_t = [t.detach().contiguous() for t in params[12:19]]
         scene = cfg.scene()
         fac = _factors_struct(sdp, sdl, sap, sal, cfg.alpha_mask[0] if cfg.alpha_mask is not None else None)
         st = _stream()
@@ -497,14 +636,11 @@ class RenderRays(torch.autograd.Function):
         count = torch.empty(R, device=dev, dtype=torch.int32)
         offset = torch.empty(R + 1, device=dev, dtype=torch.int32)
         sidx = torch.empty(R, S, device=dev, dtype=torch.int16)
-        opacity = torch.empty(R, **f32)
-        depth = torch.empty(R, **f32)
-        # only the rays want a gradient (test-time pose optimisation): the march also leaves the density feature's coordinate
-        # derivatives, taken from the taps it has in registers, and the backward reads them instead of gathering again
-        recording = getattr(cfg, "grad_enabled", True) and any(ctx.needs_input_grad)
-        ctx.pose_only = recording and not any(ctx.needs_input_grad[5:])
+        opacity, depth = torch.empty(R, **f32), torch.empty(R, **f32)
         dfeat_dn = None
-        if ctx.pose_only and POSE_MARCH_DERIVATIVES and not bool(lib.jt_set_deterministic(-1)):
+        if plan.keep_dfeat:
+            # only the rays want a gradient (test-time pose optimisation): the march also leaves the density feature's coordinate
+            # derivatives, taken from the taps it has in registers, and the backward reads them instead of gathering again
             dfeat_dn = torch.empty(3, R, S, **f32)
             check(lib.jt_march_forward_pose(scene, fac, ptr(rays_o), ptr(rays_d), ptr(jitter), ptr(zvals), R,
                                             ptr(sigma_feat), ptr(weight), ptr(tmin), ptr(count), ptr(offset), ptr(sidx),
@@ -513,9 +649,8 @@ class RenderRays(torch.autograd.Function):
             check(lib.jt_march_forward(scene, fac, ptr(rays_o), ptr(rays_d), ptr(jitter), ptr(zvals), R,
                                        ptr(sigma_feat), ptr(weight), ptr(tmin), ptr(count), ptr(offset), ptr(sidx),
                                        ptr(opacity), ptr(depth), st), "jt_march_forward")
-        ctx.dfeat_dn = dfeat_dn
-        n = cap = R * S  # worst case; kernels bound themselves by shade_offset[R] on the device
-        if cap > TAPE_SYNC_ENTRIES and not torch.cuda.is_current_stream_capturing():
+        cap = R * S  # worst case; kernels bound themselves by shade_offset[R] on the device
+        if plan.sync_sizing:
             # a batch whose worst-case tape (1.9 KB per sample) would run into tens of GB: ONE host read of the shaded
             # count the march just produced, and everything per shaded sample -- entry lists, colours, the record
             # workspace -- is sized by it (configs[3] on one GPU: 62 500 rays x 1 000 samples = 120 GB worst case,
@@ -526,7 +661,7 @@ class RenderRays(torch.autograd.Function):
             #  allocator hands the same multi-GB blocks back instead of going to hipMalloc / hipFree every iteration --
             #  measured: 814 ms per 62 500-ray step with exact sizes, 100 ms with repeating ones)
             gran = int(lib.jt_shade_chunk_entries())
-            n = cap = min(R * S, max(gran, (int(offset[R].item()) + gran - 1) // gran * gran))
+            cap = min(R * S, max(gran, (int(offset[R].item()) + gran - 1) // gran * gran))
         cap_alloc = max(cap, 1)
         eray = torch.empty(cap_alloc, device=dev, dtype=torch.int32)
         esmp = torch.empty(cap_alloc, device=dev, dtype=torch.int32)
@@ -534,36 +669,26 @@ class RenderRays(torch.autograd.Function):
         check(lib.jt_shade_list(scene, ptr(rays_d), R, ptr(offset), ptr(sidx), ptr(eray), ptr(esmp), ptr(vdir),
                                 cap, st), "jt_shade_list")
         rgb_s = torch.empty(cap_alloc, 3, **f32)
+        rgb = torch.empty(R, 3, **f32)
+        cmask = torch.empty(R, device=dev, dtype=torch.int32)
         mlp = _mlp_struct(*mlp_t)
-        if recording:
+        ws, nbytes, ticket = None, 0, 0
+        if plan.recording:
             # training: the forward leaves the layer inputs of every shaded sample in the (persistent)
             # workspace; the backward consumes them instead of gathering / evaluating the chain again
             nbytes = lib.jt_shade_workspace_bytes(scene, cap)
             ws = _workspace(dev, "shade", nbytes)
-            ctx.ws_ticket = _workspace_claim(dev, "shade")
-            # (ctx.pose_only: the light set of records)
-            ws_args = (ptr(ws), nbytes, _lib.JT_SHADE_POSE_ONLY if ctx.pose_only else 0)
-        else:
-            ws_args = (None, 0, 0)
-        timed = STEP_TIMERS is not None and ws_args[0] is not None
-        if timed:
-            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            t0.record()
+            ticket = _workspace_claim(dev, "shade")
+        tape = _Tape(cfg, cap, plan.pose_only, rays_o, rays_d, jitter, zvals, sdp, sdl, sap, sal, mlp_t, sigma_feat, weight,
+                     tmin, offset, sidx, eray, esmp, vdir, rgb_s, cmask, dfeat_dn, ticket)
+        pair = _timer_pair() if plan.timed else None
         with prof_range("compute appearance feature + Rendering"):  # tensorBase.py:774
-            check(lib.jt_shade_forward(scene, fac, mlp, ptr(rays_o), ptr(rays_d), ptr(jitter), ptr(zvals),
-                                       ptr(tmin), ptr(offset), R, ptr(eray), ptr(esmp), ptr(vdir), ptr(rgb_s),
-                                       cap, *ws_args, st), "jt_shade_forward")
-        if timed:
-            t1.record()
-            STEP_TIMERS.append(("fwd", t0, t1, offset))
-        rgb = torch.empty(R, 3, **f32)
-        cmask = torch.empty(R, device=dev, dtype=torch.int32)
+            _shade_forward(scene, fac, mlp, tape, rgb_s, ws, nbytes, st)
+        if pair is not None:
+            pair[1].record()
+            STEP_TIMERS.append(("fwd",) + pair + (offset,))
         check(lib.jt_composite_forward(scene, R, ptr(offset), ptr(sidx), ptr(weight), ptr(rgb_s), ptr(opacity),
                                        ptr(rgb), ptr(cmask), st), "jt_composite_forward")
-        ctx.cfg, ctx.n, ctx.cap = cfg, n, cap
-        ctx.saved = (rays_o, rays_d, jitter, zvals, sdp, sdl, sap, sal, mlp_t, sigma_feat, weight, tmin, offset,
-                     sidx, eray, esmp, vdir, rgb_s, cmask)
-        ctx.param_shapes = [tuple(p.shape) for p in params]
         ctx.mark_non_differentiable(depth)
         ctx.set_materialize_grads(False)  # an output nobody used arrives as None in backward, not as a zero tensor
         # which samples were shaded (device tensors, no sync): offset [R+1] exclusive scan of the per-ray counts, sidx [R,S]
@@ -571,238 +696,160 @@ class RenderRays(torch.autograd.Function):
         cfg.shade_lists = (offset, sidx)
         if KEEP_INTERMEDIATES:  # diagnostics only (tools/diag_*.py): per-sample density feature / weight of this call
             cfg.intermediates = dict(sigma_feat=sigma_feat, weight=weight, tmin=tmin)
-        # regularisers of the same factors (cfg.reg_flags = (with_tv_density, with_tv_app)): evaluated here so that
-        # the backward can ADD their gradient into the render gradient's buffer (jt_reg_losses_backward,
-        # accumulate = 1) -- as a separate autograd node the two contributions to every density factor meet in an
+        # regularisers of the same factors: evaluated here so that the backward can put their gradient into the render
+        # gradient's buffer in place -- as a separate autograd node the two contributions to every density factor meet in an
         # add kernel that allocates a third tensor (6 adds and 31 MB x 3 of traffic per iteration at 400^3)
-        reg3 = None
-        ctx.reg = None
-        flags = getattr(cfg, "reg_flags", None)
-        if flags is not None:
+        reg3 = reg = pre = None
+        if plan.reg is not None:
             hw = []
             for i in range(3):
                 H, W, _ = sdp[i].shape
                 hw += [H, W, sdl[i].shape[0]]
-            Cd, Ca = sdp[0].shape[2], sap[0].shape[2]
+            reg = ((ctypes.c_int32 * 9)(*hw), sdp[0].shape[2], sap[0].shape[2], int(bool(flags[0])), int(bool(flags[1])))
             scratch = _reg_scratch(dev)
             reg3 = torch.empty(3, **f32)
-            ctx.reg = (hw, Cd, Ca, bool(flags[0]), bool(flags[1]))
-            ctx.pre = None
-            hint = getattr(cfg, "reg_weights", None)   # dL/d reg3 as this step's loss weights will make it, if the caller knows
-            nig = ctx.needs_input_grad
-            if (hint is not None and FUSE_REG_GRADIENT and all(nig[5:14]) and _DP["world"] <= 1 and not _DP["force"]
-                    and not bool(lib.jt_set_deterministic(-1))):
-                # value AND gradient in one launch (jt_reg_losses_fused): the gradient buffers of this node's backward are
-                # created HERE, the regularisers' gradient is written into them (it covers every element of the density
-                # factors and, with TV on the colours, of the appearance planes: no zero fill for those), and the backward
-                # lets the render gradient's atomics land on top -- provided dL/d reg3 then IS the hint (checked there;
-                # otherwise the two-launch backward overwrites what was written here)
-                want_mlp = any(nig[17:24])
-                skip = (0, 1, 2) if ctx.reg[4] else (0, 1)
-                groups = [sdp, sdl, sap, sal] + ([mlp_t] if want_mlp else [])
-                outs, gflat, spans = _zeros_flat(groups, with_flat=True, unzeroed=skip)
-                gfac = _factors_struct(*outs[:4])
+            if plan.reg == "fused":
+                # value AND gradient in one launch: the gradient buffers of this node's backward are created HERE, the
+                # regularisers' gradient is written into them (it covers every element of the unzeroed groups: no zero fill for
+                # those), and the backward lets the render gradient's atomics land on top -- provided dL/d reg3 then IS the hint
+                # (checked there; otherwise the two-launch backward overwrites what was written here)
+                groups = [sdp, sdl, sap, sal] + ([mlp_t] if plan.reg_mlp else [])
+                outs, gflat, spans = _zeros_flat(groups, with_flat=True, unzeroed=plan.unzeroed)
                 if torch.is_tensor(hint):
                     w_host, w_dev = None, ptr(hint)
                 else:
                     w_host, w_dev = (ctypes.c_float * 3)(*[float(v) for v in hint]), None
-                check(lib.jt_reg_losses_fused(fac, (ctypes.c_int32 * 9)(*hw), Cd, Ca, int(ctx.reg[3]), int(ctx.reg[4]), w_host,
-                                              w_dev, gfac, ptr(scratch), ptr(reg3), st), "jt_reg_losses_fused")
-                ctx.pre = (outs, gflat, spans, hint, want_mlp)
+                check(lib.jt_reg_losses_fused(fac, *reg, w_host, w_dev, _factors_struct(*outs[:4]), ptr(scratch), ptr(reg3),
+                                              st), "jt_reg_losses_fused")
+                pre = (outs, gflat, spans, hint, plan.reg_mlp)
             else:
-                check(lib.jt_reg_losses_forward(fac, (ctypes.c_int32 * 9)(*hw), Cd, Ca, int(bool(flags[0])),
-                                                int(bool(flags[1])), ptr(scratch), ptr(reg3), st), "jt_reg_losses_forward")
+                check(lib.jt_reg_losses_forward(fac, *reg, ptr(scratch), ptr(reg3), st), "jt_reg_losses_forward")
+        ctx.tape = tape._replace(reg=reg, pre=pre)
         return rgb, depth, opacity, reg3
 
     @staticmethod
     def backward(ctx, g_rgb, g_depth, g_opacity, g_reg=None):
-        cfg = ctx.cfg
-        (rays_o, rays_d, jitter, zvals, sdp, sdl, sap, sal, mlp_t, sigma_feat, weight, tmin, offset, sidx, eray,
-         esmp, vdir, rgb_s, cmask) = ctx.saved
-        dev = rays_o.device
-        R = rays_o.shape[0]
+        t = ctx.tape
+        cfg, cap, dev, R = t.cfg, t.cap, t.rays_o.device, t.rays_o.shape[0]
         scene = cfg.scene()
-        fac = _factors_struct(sdp, sdl, sap, sal, cfg.alpha_mask[0] if cfg.alpha_mask is not None else None)
+        nig = ctx.needs_input_grad  # which groups of gradients autograd wants (test-time pose optimisation: the rays' only)
+        capturing = torch.cuda.is_current_stream_capturing()
+        plan = plan_render_backward(
+            want_fac=any(nig[5:17]), want_mlp=any(nig[17:24]),
+            det=bool(lib.jt_set_deterministic(-1)),  # JT_DETERMINISTIC: factor gradients summed in 64-bit fixed point
+            dp_on=_DP["world"] > 1 or _DP["force"], has_reg=t.reg is not None, tv_app=t.reg is not None and bool(t.reg[4]),
+            has_g_reg=g_reg is not None, hint_holds=t.pre is not None and _reg_hint_holds(g_reg, t.pre[3]),
+            pre=None if t.pre is None else t.pre[4], use_aux=_use_aux(scene), adam_early=ADAM_EARLY, capturing=capturing,
+            kept_dfeat=t.dfeat_dn is not None, timers_on=STEP_TIMERS is not None, timers_walk=STEP_TIMERS_WALK)
+        fac = _factors_struct(t.sdp, t.sdl, t.sap, t.sal, cfg.alpha_mask[0] if cfg.alpha_mask is not None else None)
+        rays = (ptr(t.rays_o), ptr(t.rays_d), ptr(t.jitter), ptr(t.zvals))
+        tmin, offset, sidx, rgb_s, cmask = ptr(t.tmin), ptr(t.offset), ptr(t.sidx), ptr(t.rgb_s), ptr(t.cmask)
         st = _stream()
         f32 = dict(device=dev, dtype=torch.float32)
         g_rgb = (torch.zeros(R, 3, **f32) if g_rgb is None else g_rgb.contiguous().float())
         g_op = None if g_opacity is None else g_opacity.contiguous().float()
-        cap, n = ctx.cap, ctx.n
         cap_alloc = max(cap, 1)
         g_rgb_s = torch.empty(cap_alloc, 3, **f32)
-        check(lib.jt_composite_backward(scene, R, ptr(offset), ptr(eray), ptr(esmp), ptr(weight), ptr(cmask),
+        check(lib.jt_composite_backward(scene, R, offset, ptr(t.eray), ptr(t.esmp), ptr(t.weight), cmask,
                                         ptr(g_rgb), ptr(g_rgb_s), cap, st), "jt_composite_backward")
-        # which groups of gradients autograd wants (test-time pose optimisation needs the rays' only)
-        nig = ctx.needs_input_grad
-        want_fac = any(nig[5:17])
-        want_mlp = any(nig[17:24])
-        fused_mlp_zero = want_fac and want_mlp
-        det = bool(lib.jt_set_deterministic(-1))  # JT_DETERMINISTIC: factor gradients summed in 64-bit fixed point
-        reg_first = False
-        if det and want_fac:
-            if _DP["world"] > 1 or _DP["force"]:
-                raise RuntimeError("JT_DETERMINISTIC is a single-process debugging mode")
-            # int64 shadow buffers with the layout of the float ones; converted after the density backward
-            (gdp, gdl, gap, gal), gflat, spans = _zeros_flat([sdp, sdl, sap, sal], with_flat=True)
-            gflat64 = torch.zeros(gflat.numel(), device=dev, dtype=torch.int64)
-            shadow = [gflat64[(v.data_ptr() - gflat.data_ptr()) // 4:][:v.numel()] for grp in (gdp, gdl, gap, gal) for v in grp]
-            gfac = _factors_struct(shadow[0:3], shadow[3:6], shadow[6:9], shadow[9:12])
-            gfac_float = _factors_struct(gdp, gdl, gap, gal)
-            fused_mlp_zero = False
-            g_mlp_z = None
-        elif want_fac and getattr(ctx, "pre", None) is not None and ctx.pre[4] == fused_mlp_zero:
-            # the forward created the buffers and wrote the regularisers' gradient for the weights it was told (ctx.pre)
-            outs, gflat, spans, hint, _ = ctx.pre
+        # gradient buffers (channel-last storage; the kernels accumulate with atomics)
+        outs = gfac = gflat = None
+        if plan.buffers == "forward":
+            outs, gflat, spans = t.pre[:3]
             # (the node must not keep a second reference to the gradient tensors it is about to return: AccumulateGrad takes a
             #  gradient over as the parameter's .grad only when nobody else holds it, and CLONES it otherwise -- seven copy
             #  launches per iteration for the basis / MLP gradients)
-            ctx.pre = None
+            ctx.tape = t = t._replace(pre=None)
+        elif plan.buffers is not None:
+            outs, gflat, spans = _zeros_flat([t.sdp, t.sdl, t.sap, t.sal, t.mlp_t][:plan.groups], with_flat=True,
+                                             unzeroed=plan.unzeroed)
+        if outs is not None:
             gdp, gdl, gap, gal = outs[:4]
-            g_mlp_z = outs[4] if fused_mlp_zero else None
-            del outs
             gfac = _factors_struct(gdp, gdl, gap, gal)
-            reg_first = True
-            if not _reg_hint_holds(g_reg, hint):
-                # dL/d reg3 is not what the forward assumed (or nobody used reg3): the two-launch form overwrites it
-                hw, Cd, Ca, wd, wa = ctx.reg
-                g3c = torch.zeros(3, **f32) if g_reg is None else g_reg.contiguous().float()
-                check(lib.jt_reg_losses_backward(fac, (ctypes.c_int32 * 9)(*hw), Cd, Ca, ptr(g3c), int(wd), int(wa), gfac, 0,
-                                                 ptr(torch.empty(36, **f32)), st), "jt_reg_losses_backward")
-                REG_FUSION_STATS["rewritten"] += 1
-            else:
-                REG_FUSION_STATS["trusted"] += 1
-        elif want_fac:
-            # gradient buffers (channel-last storage; the kernels accumulate with atomics).  Single process with the
-            # regularisers in this node: their gradient covers every element of the density factors (L1) and, with TV on
-            # the colours, of the appearance planes -- it is WRITTEN first, in place of those tensors' zero fill (the
-            # atomics of the render backward then land on top of it; before: fill + read-modify-write of the same bytes)
-            reg_first = (ctx.reg is not None and g_reg is not None and _DP["world"] <= 1 and not _DP["force"])
-            skip = ((0, 1, 2) if ctx.reg[4] else (0, 1)) if reg_first else ()
-            if fused_mlp_zero:
-                (gdp, gdl, gap, gal, g_mlp_z), gflat, spans = _zeros_flat([sdp, sdl, sap, sal, mlp_t], with_flat=True,
-                                                                          unzeroed=skip)
-            else:
-                (gdp, gdl, gap, gal), gflat, spans = _zeros_flat([sdp, sdl, sap, sal], with_flat=True, unzeroed=skip)
-            gfac = _factors_struct(gdp, gdl, gap, gal)
-            if reg_first:
-                hw, Cd, Ca, wd, wa = ctx.reg
-                scratch = torch.empty(36, **f32)
-                g3c = g_reg.contiguous().float()
-                check(lib.jt_reg_losses_backward(fac, (ctypes.c_int32 * 9)(*hw), Cd, Ca, ptr(g3c), int(wd), int(wa), gfac, 0,
-                                                 ptr(scratch), st), "jt_reg_losses_backward")
-        else:
-            gfac = None
+        if plan.buffers == "shadow":
+            # int64 shadow buffers with the layout of the float ones; converted after the density backward
+            gflat64 = torch.zeros(gflat.numel(), device=dev, dtype=torch.int64)
+            shadow = [gflat64[(v.data_ptr() - gflat.data_ptr()) // 4:][:v.numel()] for grp in outs for v in grp]
+            gfac_float, gfac = gfac, _factors_struct(shadow[0:3], shadow[3:6], shadow[6:9], shadow[9:12])
+        if plan.reg_before == "trusted":
+            REG_FUSION_STATS["trusted"] += 1
+        elif plan.reg_before is not None:
+            # "overwrite": dL/d reg3 is not what the forward assumed (or nobody used reg3); "write": in place of the zero fill
+            _reg_backward(t.reg, fac, g_reg, gfac, 0, dev, st)
+            REG_FUSION_STATS["rewritten"] += plan.reg_before == "overwrite"
         g_xyz = torch.empty(cap_alloc, 3, **f32)
-        join = None
-        g_mlp = [None] * 7
         if _EARLY_GRADS:
             _EARLY_GRADS.pop(device_key(dev), None)  # (an earlier backward's offer nobody took)
-        dp_on = _DP["world"] > 1 or _DP["force"]
-        dp = dp_on and fused_mlp_zero
-        if dp_on and not dp and (want_fac or want_mlp):
-            raise RuntimeError("data-parallel render backward needs the fused path with all scene gradients wanted")
-
-        reducer = DpReducer(gflat, spans, _DP["group"]) if dp else None
-        mlp = _mlp_struct(*mlp_t)
-        if want_mlp:
-            g_mlp = g_mlp_z if fused_mlp_zero else [torch.zeros_like(t) for t in mlp_t]
-            gm = _mlp_struct(*g_mlp)
-        else:
-            gm = None
+        reducer = DpReducer(gflat, spans, _DP["group"]) if plan.dp else None
+        mlp = _mlp_struct(*t.mlp_t)
+        g_mlp = outs[4] if plan.mlp == "carved" else [torch.zeros_like(x) for x in t.mlp_t] if plan.mlp else [None] * 7
+        gm = _mlp_struct(*g_mlp) if plan.mlp else None
         nbytes = lib.jt_shade_workspace_bytes(scene, cap)
         ws = _workspace(dev, "shade", nbytes)
-        if _workspace_owner(dev, "shade") != ctx.ws_ticket:
+        if _workspace_owner(dev, "shade") != t.ws_ticket:
             # another render wrote the workspace since this one's forward (several forwards before one
             # backward): put this call's records back
-            ctx.ws_ticket = _workspace_claim(dev, "shade")
-            check(lib.jt_shade_forward(scene, fac, mlp, ptr(rays_o), ptr(rays_d), ptr(jitter), ptr(zvals),
-                                       ptr(tmin), ptr(offset), R, ptr(eray), ptr(esmp), ptr(vdir),
-                                       ptr(torch.empty_like(rgb_s)), cap, ptr(ws), nbytes,
-                                       _lib.JT_SHADE_POSE_ONLY if ctx.pose_only else 0, st),
-                  "jt_shade_forward")
-        use_aux = _use_aux(scene)
-        if use_aux and want_mlp:
-            aux, ev_fork, ev_join = _aux_stream(dev)
+            ctx.tape = t = t._replace(ws_ticket=_workspace_claim(dev, "shade"))
+            _shade_forward(scene, fac, mlp, t, torch.empty_like(t.rgb_s), ws, nbytes, st)
+        h_aux, join = (None, None, None), None
+        if plan.fork:
+            aux, ev_fork, join = _aux_stream(dev)
             # the weight-gradient GEMMs read mlp_t / ws and write g_mlp on the auxiliary stream
-            if not torch.cuda.is_current_stream_capturing():  # graph-pool memory is never recycled elsewhere
-                for t in list(mlp_t) + g_mlp + [offset]:
-                    t.record_stream(aux)
-            h_aux = (ctypes.c_void_p(aux.cuda_stream), ctypes.c_void_p(ev_fork.cuda_event),
-                     ctypes.c_void_p(ev_join.cuda_event))
-            join = ev_join
-        else:
-            h_aux = (None, None, None)
-        t_bwd_end = None
-        if STEP_TIMERS is not None and not ctx.pose_only:
-            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            t0.record()
-            if h_aux[0] is not None:
-                # the weight-gradient GEMMs go to the auxiliary stream: what this call leaves on the launch stream IS the
-                # per-sample backward (k_shade_bwd, or chain + scatter when split) -- its end mark is recorded behind the call
-                t_bwd_end = t1
-                # ... and the fork event the library records BEHIND THE CHAIN (split backward: the GEMMs wait for it) is a
-                # timing event of this launch's own while the step timers are on: chain and scatter are told apart
-                t_mid = torch.cuda.Event(enable_timing=True)
-                t_mid.record()  # creates the handle
-                h_aux = (h_aux[0], ctypes.c_void_p(t_mid.cuda_event), h_aux[2])
-                STEP_TIMERS.append(("bwd_chain", t0, t_mid, offset))
-                STEP_TIMERS.append(("bwd_scatter", t_mid, t1, offset))
-            else:
-                # one stream: the library records the mark between the per-sample kernels and the GEMMs (jt_render.h)
-                t1.record()  # creates the handle
-                h_aux = (h_aux[0], ctypes.c_void_p(t1.cuda_event), h_aux[2])
-            STEP_TIMERS.append(("bwd", t0, t1, offset))
-        check(lib.jt_shade_backward(scene, fac, mlp, ptr(rays_o), ptr(rays_d), ptr(jitter), ptr(zvals),
-                                    ptr(tmin), ptr(offset), R, ptr(eray), ptr(esmp), ptr(vdir), ptr(rgb_s),
+            if not capturing:  # graph-pool memory is never recycled elsewhere
+                for x in list(t.mlp_t) + g_mlp + [t.offset]:
+                    x.record_stream(aux)
+            h_aux = (ctypes.c_void_p(aux.cuda_stream), ctypes.c_void_p(ev_fork.cuda_event), ctypes.c_void_p(join.cuda_event))
+        if plan.timers:
+            # forked: what the call leaves on the launch stream IS the per-sample backward (k_shade_bwd, or chain + scatter when
+            # split) -- its end mark is recorded behind the call -- and the fork event the library records BEHIND THE CHAIN (the
+            # GEMMs wait for it) is a timing event of this launch's own: chain and scatter are told apart.  One stream: the
+            # library records the end mark between the per-sample kernels and the GEMMs (jt_render.h)
+            t0, t1 = _timer_pair()
+            t_mark = torch.cuda.Event(enable_timing=True) if plan.fork else t1
+            t_mark.record()  # creates the handle
+            h_aux = (h_aux[0], ctypes.c_void_p(t_mark.cuda_event), h_aux[2])
+            marks = {"bwd_chain": (t0, t_mark), "bwd_scatter": (t_mark, t1), "bwd": (t0, t1)}
+            STEP_TIMERS.extend((kind,) + marks[kind] + (t.offset,) for kind in plan.timers)
+        check(lib.jt_shade_backward(scene, fac, mlp, *rays, tmin, offset, R, ptr(t.eray), ptr(t.esmp), ptr(t.vdir), rgb_s,
                                     ptr(g_rgb_s), gfac, gm, ptr(g_xyz), cap, ptr(ws), nbytes, 0, st, *h_aux),
               "jt_shade_backward")
-        if t_bwd_end is not None:
-            t_bwd_end.record()
-        if dp:
+        if plan.timers and plan.fork:
+            t1.record()
+        if plan.dp:
             reducer.reduce(2, 3)  # appearance planes + lines are final
-        elif (ADAM_EARLY and want_fac and not det and use_aux and (reg_first or ctx.reg is None or g_reg is None)
-              and not torch.cuda.is_current_stream_capturing()):
+        elif plan.early:
             # the appearance factors' gradients are final HERE (their regulariser part was written before the render backward);
             # what follows on this stream -- the density backward -- is bound by the float-atomic path and leaves the memory
             # system idle: an optimizer that asks (optim.VMAdam.step -> take_early_grads) steps these tensors on the auxiliary
             # stream, beside the density walk, and the rest behind it as before
             ev = _early_event(dev)
             ev.record()
-            _EARLY_GRADS[device_key(dev)] = (ev, frozenset(int(t.data_ptr()) for t in list(gap) + list(gal)), gflat)
-        g_o = torch.empty(R, 3, **f32)
-        g_d = torch.empty(R, 3, **f32)
+            _EARLY_GRADS[device_key(dev)] = (ev, frozenset(int(x.data_ptr()) for x in list(gap) + list(gal)), gflat)
+        g_o, g_d = torch.empty(R, 3, **f32), torch.empty(R, 3, **f32)
         mws_bytes = lib.jt_march_backward_workspace_bytes(scene, R)
         mws = _workspace(dev, "march_bwd", mws_bytes)
-        timed = STEP_TIMERS is not None and STEP_TIMERS_WALK and not getattr(ctx, "pose_only", False)
-        if timed:
-            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            t0.record()
-        if getattr(ctx, "dfeat_dn", None) is not None and gfac is None:
-            check(lib.jt_march_backward_pose(scene, fac, ptr(rays_o), ptr(rays_d), ptr(jitter), ptr(zvals), R,
-                                             ptr(sigma_feat), ptr(weight), ptr(tmin), ptr(offset), ptr(sidx), ptr(rgb_s),
-                                             ptr(cmask), ptr(g_rgb), ptr(g_op), ptr(g_xyz), ptr(ctx.dfeat_dn), ptr(g_o), ptr(g_d),
+        pair = _timer_pair() if plan.walk_timed else None
+        if plan.march_pose:
+            check(lib.jt_march_backward_pose(scene, fac, *rays, R, ptr(t.sigma_feat), ptr(t.weight), tmin, offset, sidx, rgb_s,
+                                             cmask, ptr(g_rgb), ptr(g_op), ptr(g_xyz), ptr(t.dfeat_dn), ptr(g_o), ptr(g_d),
                                              ptr(mws), mws_bytes, st), "jt_march_backward_pose")
         else:
-            check(lib.jt_march_backward(scene, fac, ptr(rays_o), ptr(rays_d), ptr(jitter), ptr(zvals), R,
-                                        ptr(sigma_feat), ptr(weight), ptr(tmin), ptr(offset), ptr(sidx), ptr(rgb_s),
-                                        ptr(cmask), ptr(g_rgb), ptr(g_op), ptr(g_xyz), gfac, ptr(g_o), ptr(g_d),
+            check(lib.jt_march_backward(scene, fac, *rays, R, ptr(t.sigma_feat), ptr(t.weight), tmin, offset, sidx, rgb_s,
+                                        cmask, ptr(g_rgb), ptr(g_op), ptr(g_xyz), gfac, ptr(g_o), ptr(g_d),
                                         ptr(mws), mws_bytes, st), "jt_march_backward")
-        if timed:
-            t1.record()
-            # listed samples of this call (in-box samples with a density gradient): the per-ray counts sit behind
-            # gfeat [R,S] f32 and vlist [R,S] u16 in the workspace (jt_march.hip: march_bwd_ws_layout)
-            S_ = cfg.n_samples
-            o = (R * S_ * 4 + 255) // 256 * 256
-            o = (o + R * S_ * 2 + 255) // 256 * 256
-            STEP_TIMERS.append(("march_bwd", t0, t1, mws[o:o + 4 * R].view(torch.int32).sum().view(1)))
-        if dp:
+        if pair is not None:
+            pair[1].record()
+            # listed samples of this call (in-box samples with a density gradient)
+            o = march_bwd_counts_offset(R, cfg.n_samples)
+            STEP_TIMERS.append(("march_bwd",) + pair + (mws[o:o + 4 * R].view(torch.int32).sum().view(1),))
+        if plan.dp:
             reducer.reduce(0, 1)  # density planes + lines are final
         if join is not None:
             torch.cuda.current_stream().wait_event(join)  # weight gradients done before anyone reads them
-        if dp:
+        if plan.dp:
             reducer.reduce(4, 4)  # basis + MLP
             reducer.wait()  # stream-level: whoever consumes the gradients next runs behind the collectives
-        if det and want_fac:
+        if plan.buffers == "shadow":
             # fixed point -> float (value = word / 2^48), in place of the zero-filled float buffers; a sum at or beyond
             # 2^60 (value 4 096: out of the format's safe range) leaves the FINITE_GRAD bit in the device's status word --
             # read with the other non-finite checks (read_status); a non-finite ADDEND was dropped by the kernels and
@@ -811,21 +858,12 @@ class RenderRays(torch.autograd.Function):
             bad = (gflat64.abs() >= (1 << 60)).any()
             status_word(dev).bitwise_or_(bad.to(torch.int32) * FINITE_GRAD)
             gfac = gfac_float
-        if reg_first:
-            pass  # written before the render backward, above
-        elif ctx.reg is not None and g_reg is not None and want_fac:
+        if plan.reg_after:
             # the regularisers' gradient joins the render gradient in place (after the collectives: it is the same
             # on every rank and is not part of the exchange; after the fixed-point conversion in deterministic mode)
-            hw, Cd, Ca, wd, wa = ctx.reg
-            scratch = torch.empty(36, **f32)
-            g3c = g_reg.contiguous().float()
-            check(lib.jt_reg_losses_backward(fac, (ctypes.c_int32 * 9)(*hw), Cd, Ca, ptr(g3c), int(wd), int(wa), gfac, 1,
-                                             ptr(scratch), st), "jt_reg_losses_backward")
-        elif ctx.reg is not None and g_reg is not None:
-            raise RuntimeError("regulariser gradient wanted without factor gradients")
-        g_factors = [factor_logical(t) for t in gdp + gdl + gap + gal] if want_fac else [None] * 12
-        out = [None, g_o, g_d, None, None] + g_factors + list(g_mlp)
-        return tuple(out)
+            _reg_backward(t.reg, fac, g_reg, gfac, 1, dev, st)
+        g_factors = [factor_logical(x) for x in gdp + gdl + gap + gal] if outs is not None else [None] * 12
+        return tuple([None, g_o, g_d, None, None] + g_factors + list(g_mlp))
 
 
 def render_rays(cfg, rays_o, rays_d, jitter, zvals, density_plane, density_line, app_plane, app_line, basis,
