@@ -139,6 +139,9 @@ __global__ void k_render_loss_final(const float* __restrict__ acc, float fe, flo
   }
 }
 
+// A NaN colour is excluded from the mean and gets the gradient g x 0 = 0.  torch's nanmean backward gives NaN there (0 x 2 NaN
+// through the square): the difference is deliberate.  The reference takes nanmean "to ignore the nan pixels" (model/base.py:261);
+// a NaN gradient would reach every parameter the ray touches, and the NaN colour itself is reported by the finiteness guard.
 __global__ __launch_bounds__(256) void k_render_loss_bwd(const float* __restrict__ rgb, const float* __restrict__ image,
                                                          const int64_t* __restrict__ ray_idx,
                                                          const uint8_t* __restrict__ mask, int B, int r, int HW,
@@ -170,7 +173,8 @@ __global__ __launch_bounds__(256) void k_render_loss_bwd(const float* __restrict
 // ---- one photometric mean PER VIEW over a ragged batch (batched test-time pose optimisation, model/bat.py:265-292) -------------
 // view b owns rays voff[b] .. voff[b + 1] - 1 of rgb [n][3] / ray_idx [n]; image [V][3][HW].  One workgroup per view, with the
 // summation structure of k_render_loss_fwd_one for a single view: loss[b] and the backward's per-element gradient are the
-// single-view launch's bit for bit.
+// single-view launch's bit for bit -- for views of 3 r <= 32 768 colours; past that the single-view entry point sums with
+// k_render_loss_fwd (256-thread workgroups, atomic adds) and the two agree to rounding only.
 __global__ __launch_bounds__(1024) void k_render_loss_views_fwd(const float* __restrict__ rgb, const float* __restrict__ image,
                                                                 const int64_t* __restrict__ ray_idx,
                                                                 const int* __restrict__ voff, int HW,

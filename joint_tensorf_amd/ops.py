@@ -1480,7 +1480,9 @@ def ray_gen_ragged(pose, intr_inv, intr, ray_idx, view_offset, image_w, ndc=Fals
 
 class RenderLossViews(torch.autograd.Function):
     """one photometric nanmean PER VIEW over a ragged batch: rgb [n, 3], image [V, 3, H, W], ray_idx [n], view_offset [V + 1]
-    -> loss [V] (jt_render_loss_views_*: the single-view RenderLoss bit for bit, view by view)."""
+    -> loss [V] (jt_render_loss_views_*: the single-view RenderLoss bit for bit, view by view, for views of 3 r <= 32 768
+    colours; a larger view alone takes RenderLoss' multi-workgroup kernel and agrees to rounding only).  An empty view's loss
+    is NaN (0 / 0)."""
 
     @staticmethod
     def forward(ctx, rgb, image, ray_idx, view_offset):
