@@ -367,7 +367,7 @@ int jt_shade_set_lean_tape(int on);
  *   [8]  its dynamic LDS bytes   [9] its workgroups at most (also the slab count k_dbasis_reduce sums)
  *   [10] lean tape   [11] rows of a tile's record block (= jt_shade_record_layout out[0])
  *   [12] dBasis is formed in the scatter
- *   [13] weight-gradient GEMMs: 0 k_wgrad (fp32), 1 k_wgrad_b16   [14] GEMMs per chunk (0, 3 or 4)   [15] on the auxiliary stream
+ *   [13] weight-gradient GEMMs k_wgrad<.., B16>: 0 <.., false> (fp32), 1 <.., true> (bf16)   [14] GEMMs per chunk (0, 3 or 4)   [15] on the auxiliary stream
  * JT_ERR_UNSUPPORTED for a NULL argument, a scene kind the shade kernels are not built for, or a plan without an instantiation. */
 int jt_shade_backward_plan(const JtScene* scene, int want_factor_grads, int want_mlp_grads, int flags, int have_aux,
                            int32_t* out16);

@@ -697,7 +697,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // step's flush atomics (a wave's vector-memory operations retire in order), and paid + 0.6 ms for it.  2 NCH accumulator quads
 // per lane; a plane's slice is summed over the waves in LDS in a fixed order and left in the workgroup's slab for
 // k_dbasis_reduce.  With it the forward does not record the 3 Ca products (576 of 1 920 bytes per sample for VM-48) and the
-// dBasis GEMM (k_wgrad_b16<1, NTB, 0>, 184 us alone) is gone.
+// dBasis GEMM (k_wgrad<1, NTB, 0, 0, true>, 184 us alone) is gone.
 // The plane loop is OUTSIDE the batch loop (one LDS line at a time): the coordinate gradients of a sample go to g_xyz as
 // store (plane 0) / load-add-store (planes 1, 2) by the same lane.
 template <class C, bool DET, int RUN, int WAVES, int FLAGS>
@@ -1153,9 +1153,6 @@ __global__ __launch_bounds__(256, 3) void k_pose_gather(Dev D, MlpDev M, const i
 namespace jt {
 
 // ---- weight gradients: dW[m][n] += sum_p A[p][m] * B[p][n],  db[m] += sum_p A[p][m] ------------------------
-// A skinny GEMM over the sample axis with v_mfma_f32_32x32x2_f32: the two lane halves take two consecutive
-// samples per step, lane & 31 is the unit index for both operands (coalesced 128-byte row reads).
-// XF = 1 / 2 builds the layer-1 input row [f, d, PE(f), PE(d)] / [f, PE(f)] on the fly from the F record.
 // Column of the layer-1 weight matrix that N-tile b, lane m of the weight-gradient GEMM stands for.
 // Tile 0 holds the raw inputs (features, then the view direction for MLP_Fea), tile t = 1..4 holds
 // positional-encoding function t of the SAME source scalar, so a lane evaluates sin/cos once per sample
@@ -1167,13 +1164,7 @@ __device__ inline int l1_column(int b, int m, int APP) {
   return -1;
 }
 
-// ---- weight gradients: dW[m][n] += sum_p A[p][m] * B[p][n],  db[m] += sum_p A[p][m] ------------------------
-// A skinny GEMM over the sample axis with v_mfma_f32_32x32x2_f32.  The records are tile-blocked
-// ([row][32 samples]), and the MFMA wants the unit on the lane (lane & 31) and the sample on the k axis
-// (lane half + step): every lane therefore reads ITS unit's 128-byte row of the tile with eight 16-byte
-// loads (the same access shape as the factor gather) and feeds its 16 same-parity samples step by step --
-// no LDS, no transposition.  XF = 1 / 2: B is the layer-1 input [f, d, PE(f), PE(d)] / [f, PE(f)]: lane m
-// loads the row of source scalar m once, takes sin/cos once per sample and serves all five N tiles.
+// N tile b of the layer-1 input for source scalar x: x itself, then its four positional-encoding functions
 template <int XF>
 __device__ inline float pe_pick(int b, float x, float sn, float cs, float m0, float m1) {
   return (b == 0) ? x : (b == 1) ? sn * m0 : (b == 2) ? 2.f * sn * cs * m1 : (b == 3) ? cs * m0
@@ -1279,7 +1270,31 @@ __device__ inline void g2_derive(const float (*raw)[16], const float (*w)[3], in
     }
 }
 
-template <int MT, int NT, int XF, int XA = 0>
+// Keep the use of sixteen prefetched values BEHIND whatever loads were issued in front of this point.  The instruction selector
+// orders pure arithmetic by data dependence only: without a pin it places the consumer of a row directly behind that row's own
+// loads, i.e. in front of the NEXT row's prefetch, and the "one step ahead" of the loops below turns into a full wait
+// (s_waitcnt vmcnt(0)) behind every load (JT_WGRAD_PIN = 0 shows it in the listing).
+#ifndef JT_WGRAD_PIN
+#define JT_WGRAD_PIN 1
+#endif
+__device__ inline void pin16(float v[16]) {
+#if JT_WGRAD_PIN
+#pragma unroll
+  for (int q = 0; q < 16; q += 4) asm volatile("" : "+v"(v[q]), "+v"(v[q + 1]), "+v"(v[q + 2]), "+v"(v[q + 3]));
+#endif
+}
+
+// A skinny GEMM over the sample axis with v_mfma_f32_32x32x2_f32.  The records are tile-blocked ([row][32 samples]), and the
+// MFMA wants the unit on the lane (lane & 31) and the sample on the k axis (lane half + step): every lane therefore reads ITS
+// unit's 128-byte row of the tile with eight 16-byte loads (the same access shape as the factor gather) and feeds its 16
+// same-parity samples step by step -- no LDS, no transposition.  XF = 1 / 2: B is the layer-1 input [f, d, PE(f), PE(d)] /
+// [f, PE(f)]: lane m loads the row of source scalar m once, takes sin/cos once per sample and serves all five N tiles.
+// B16: the same skinny GEMM on the bf16 matrix cores at fp32-level accuracy (jt_shade_core.h, "bf16x3"): both operands are
+// per-sample data here, so both are split in registers -- (MT + NT) x 16 values per lane and tile -- and a tile's 32 samples
+// are two 16-deep K steps (lane half h feeds samples 16 h + 8 s .. + 7 to step s: the contraction order is free as long as
+// A and B agree).  Per (M tile, N tile) and tile of samples: 12 MFMAs of 32 cycles instead of 16 of 64.  The two paths differ
+// in pin, prepA and product below and in the look-ahead load (fp32: conditional; B16: clamped and unconditional).
+template <int MT, int NT, int XF, int XA, bool B16>
 __global__ __launch_bounds__(256) void k_wgrad(const float* __restrict__ rec, int a_row0, int M, int b_row0, int N,
                                                int f_row0, int vd_row0, int rec_rows, PeMask pm, int APP,
                                                const int* __restrict__ offset, int R, int cap, int chunk_start,
@@ -1306,7 +1321,7 @@ __global__ __launch_bounds__(256) void k_wgrad(const float* __restrict__ rec, in
       for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
   }
   // The contraction runs over the samples of a tile in any order: lane half h takes samples 16 h .. 16 h + 15
-  // (MFMA step q pairs sample q with sample 16 + q), so a lane reads 64 contiguous bytes of its unit's row.
+  // (fp32 MFMA step q pairs sample q with sample 16 + q), so a lane reads 64 contiguous bytes of its unit's row.
   // Rows are fetched one step ahead of the MFMAs that consume them (next B row, or the next tile's A rows).
   const size_t tstride = (size_t)rec_rows * 32;
   auto loadA = [&](int t, float (*dst)[16]) {
@@ -1317,6 +1332,36 @@ __global__ __launch_bounds__(256) void k_wgrad(const float* __restrict__ rec, in
     }
   };
   float av[MT][16], an[MT][16];
+  B3 a3[B16 ? MT : 1][2];
+  auto pin = [](float v[16]) { if constexpr (B16) pin16(v); };
+  // A of the current tile: masked, summed for the bias gradient and, for B16, split once for all N tiles.  (It is handed av
+  // and a3 as A and A3 and must not capture them: with av captured the compiler rounds g2_derive's sum differently for single
+  // samples, and the last place of dW2 moves.  The zeroing loops above, not `= {}`, keep the B16 listings as they were.)
+  auto prepA = [&](float (*A)[16], int nl, B3 (*A3)[2]) {
+#pragma unroll
+    for (int a = 0; a < MT; ++a) {
+      if (nl < 32) mask_tail(A[a], h, nl);
+#pragma unroll
+      for (int q = 0; q < 16; ++q) asum[a] += A[a][q];
+      if constexpr (B16) A3[a][0] = split8(A[a]), A3[a][1] = split8(A[a] + 8);
+    }
+  };
+  auto product = [&](int b, const float* bv) {
+    if constexpr (B16) {
+      const B3 b0 = split8(bv), b1 = split8(bv + 8);
+#pragma unroll
+      for (int a = 0; a < MT; ++a) {
+        acc[a][b] = mfma6(a3[a][0], b0, acc[a][b]);
+        acc[a][b] = mfma6(a3[a][1], b1, acc[a][b]);
+      }
+    } else {
+#pragma unroll
+      for (int q = 0; q < 16; ++q)
+#pragma unroll
+        for (int a = 0; a < MT; ++a)
+          acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[a][q], bv[q], acc[a][b], 0, 0, 0);
+    }
+  };
   float gw[MT][3], raw[XA ? 4 : 1][16], rawn[XA ? 4 : 1][16];
   if (XA) {
 #pragma unroll
@@ -1339,188 +1384,12 @@ __global__ __launch_bounds__(256) void k_wgrad(const float* __restrict__ rec, in
       const int nl = min(32, n - t * 32);
 #pragma unroll
       for (int b = 0; b < NT; ++b) {
+        // (B16: unconditionally -- the last step of the last tile fetches its own rows again: with the loads under control flow
+        //  the wait-count pass gives up and waits for everything)
         if (b + 1 < NT) {
           loadB(t, b + 1, bn);
-        } else if (t + 1 < t_end) {
-          if (XA) g2_load_raw(rec + (size_t)(t + 1) * tstride, gs, m, h, rawn);
-          else loadA(t + 1, an);
-          loadB(t + 1, 0, bn);
-        }
-        if (b == 0) {
-          if (XA) g2_derive<MT>(raw, gw, m, av);
-          if (nl < 32) {
-#pragma unroll
-            for (int a = 0; a < MT; ++a) mask_tail(av[a], h, nl);
-          }
-#pragma unroll
-          for (int a = 0; a < MT; ++a)
-#pragma unroll
-            for (int q = 0; q < 16; ++q) asum[a] += av[a][q];
-        }
-        if (nl < 32) mask_tail(bv, h, nl);  // never-written record slots may hold anything, 0 * NaN is NaN
-#pragma unroll
-        for (int q = 0; q < 16; ++q)
-#pragma unroll
-          for (int a = 0; a < MT; ++a)
-            acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[a][q], bv[q], acc[a][b], 0, 0, 0);
-#pragma unroll
-        for (int q = 0; q < 16; ++q) bv[q] = bn[q];
-      }
-      if (XA) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-#pragma unroll
-          for (int q = 0; q < 16; ++q) raw[XA ? c : 0][q] = rawn[XA ? c : 0][q];
-      } else {
-#pragma unroll
-      for (int a = 0; a < MT; ++a)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) av[a][q] = an[a][q];
-      }
-    }
-  } else {
-    const bool feat = m < APP, view = (XF == 1) && !feat && (m < APP + 3);
-    const int srow = feat ? f_row0 + m : vd_row0 + (view ? m - APP : 0);
-    const float m0 = view ? pm.v0 : pm.f0, m1 = view ? pm.v1 : pm.f1;
-    const bool live = feat || view;
-    float x[16], xn[16];
-    if (t_begin < t_end) {
-      loadA(t_begin, av);
-      load_row_half(rec + (size_t)t_begin * tstride + (size_t)srow * 32, live, h, x);
-    }
-    for (int t = t_begin; t < t_end; ++t) {
-      const int nl = min(32, n - t * 32);
-      if (t + 1 < t_end) {
-        loadA(t + 1, an);
-        load_row_half(rec + (size_t)(t + 1) * tstride + (size_t)srow * 32, live, h, xn);
-      }
-      if (nl < 32) {
-#pragma unroll
-        for (int a = 0; a < MT; ++a) mask_tail(av[a], h, nl);
-        mask_tail(x, h, nl);  // never-written record slots may hold anything, 0 * NaN is NaN
-      }
-#pragma unroll
-      for (int a = 0; a < MT; ++a)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) asum[a] += av[a][q];
-      float sn[16], cs[16];
-#pragma unroll
-      for (int q = 0; q < 16; ++q) sincos_grad(x[q], &sn[q], &cs[q]);
-#pragma unroll
-      for (int b = 0; b < NT; ++b) {
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-          // the A operand is zero past nl, so the (finite) encoding of a padding sample never contributes
-          const float bv = live ? pe_pick<XF>(b, x[q], sn[q], cs[q], m0, m1) : 0.f;
-#pragma unroll
-          for (int a = 0; a < MT; ++a)
-            acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[a][q], bv, acc[a][b], 0, 0, 0);
-        }
-      }
-#pragma unroll
-      for (int q = 0; q < 16; ++q) x[q] = xn[q];
-#pragma unroll
-      for (int a = 0; a < MT; ++a)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) av[a][q] = an[a][q];
-    }
-  }
-  wgrad_epilogue<MT, NT>(acc, asum, s_red, slab, lane, wv, m, h);
-}
-
-// Keep the use of sixteen prefetched values BEHIND whatever loads were issued in front of this point.  The instruction selector
-// orders pure arithmetic by data dependence only: without a pin it places the consumer of a row directly behind that row's own
-// loads, i.e. in front of the NEXT row's prefetch, and the "one step ahead" of the loops below turns into a full wait
-// (s_waitcnt vmcnt(0)) behind every load (JT_WGRAD_PIN = 0 shows it in the listing).
-#ifndef JT_WGRAD_PIN
-#define JT_WGRAD_PIN 1
-#endif
-__device__ inline void pin16(float v[16]) {
-#if JT_WGRAD_PIN
-#pragma unroll
-  for (int q = 0; q < 16; q += 4) asm volatile("" : "+v"(v[q]), "+v"(v[q + 1]), "+v"(v[q + 2]), "+v"(v[q + 3]));
-#endif
-}
-
-// The same skinny GEMM on the bf16 matrix cores at fp32-level accuracy (jt_shade_core.h, "bf16x3"): both operands are
-// per-sample data here, so both are split in registers -- (MT + NT) x 16 values per lane and tile -- and a tile's 32 samples
-// are two 16-deep K steps (lane half h feeds samples 16 h + 8 s .. + 7 to step s: the contraction order is free as long as
-// A and B agree).  Per (M tile, N tile) and tile of samples: 12 MFMAs of 32 cycles instead of 16 of 64.
-template <int MT, int NT, int XF, int XA = 0>
-__global__ __launch_bounds__(256) void k_wgrad_b16(const float* __restrict__ rec, int a_row0, int M, int b_row0, int N,
-                                                   int f_row0, int vd_row0, int rec_rows, PeMask pm, int APP,
-                                                   const int* __restrict__ offset, int R, int cap, int chunk_start,
-                                                   int chunk_cap, float* __restrict__ slab, G2Src gs) {
-  __shared__ float s_red[4][16][64];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int m = lane & 31, h = lane >> 5;
-  const int total = min(offset[R], cap);
-  const int n = min(total - chunk_start, chunk_cap);
-  if (n <= 0) return;
-  const int ntiles = (n + 31) >> 5;
-  const int per = wgrad_tiles_per_wave(n, gridDim.x);
-  if ((int)blockIdx.x >= wgrad_active_blocks(n, gridDim.x)) return;
-  const int w = blockIdx.x * 4 + wv;
-  const int t_begin = min(w * per, ntiles), t_end = min(t_begin + per, ntiles);
-  f32x16 acc[MT][NT];
-  float asum[MT];
-#pragma unroll
-  for (int a = 0; a < MT; ++a) {
-    asum[a] = 0.f;
-#pragma unroll
-    for (int b = 0; b < NT; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-  }
-  const size_t tstride = (size_t)rec_rows * 32;
-  auto loadA = [&](int t, float (*dst)[16]) {
-#pragma unroll
-    for (int a = 0; a < MT; ++a) {
-      const int c = a * 32 + m;
-      load_row_half(rec + (size_t)t * tstride + (size_t)(a_row0 + min(c, M - 1)) * 32, c < M, h, dst[a]);
-    }
-  };
-  // A of the current tile: masked, summed for the bias gradient, split once for all N tiles
-  auto prepA = [&](float (*av)[16], int nl, B3 (*a3)[2]) {
-#pragma unroll
-    for (int a = 0; a < MT; ++a) {
-      if (nl < 32) mask_tail(av[a], h, nl);
-#pragma unroll
-      for (int q = 0; q < 16; ++q) asum[a] += av[a][q];
-      a3[a][0] = split8(av[a]);
-      a3[a][1] = split8(av[a] + 8);
-    }
-  };
-  float av[MT][16], an[MT][16];
-  B3 a3[MT][2];
-  float gw[MT][3], raw[XA ? 4 : 1][16], rawn[XA ? 4 : 1][16];
-  if (XA) {
-#pragma unroll
-    for (int a = 0; a < MT; ++a)
-#pragma unroll
-      for (int c = 0; c < 3; ++c) gw[a][c] = (a * 32 + m < M) ? gs.w3[c * gs.in3 + gs.hoff + a * 32 + m] : 0.f;
-  }
-  if (XF == 0) {
-    auto loadB = [&](int t, int b, float* dst) {
-      const int c = b * 32 + m;
-      load_row_half(rec + (size_t)t * tstride + (size_t)(b_row0 + min(c, N - 1)) * 32, c < N, h, dst);
-    };
-    float bv[16], bn[16];
-    if (t_begin < t_end) {
-      if (XA) g2_load_raw(rec + (size_t)t_begin * tstride, gs, m, h, raw);
-      else loadA(t_begin, av);
-      loadB(t_begin, 0, bv);
-    }
-    for (int t = t_begin; t < t_end; ++t) {
-      const int nl = min(32, n - t * 32);
-#pragma unroll
-      for (int b = 0; b < NT; ++b) {
-        // (unconditionally -- the last step of the last tile fetches its own rows again: with the loads under control flow the
-        //  wait-count pass gives up and waits for everything)
-        if (b + 1 < NT) {
-          loadB(t, b + 1, bn);
-        } else {
-          const int tn = min(t + 1, t_end - 1);
+        } else if (B16 || t + 1 < t_end) {
+          const int tn = B16 ? min(t + 1, t_end - 1) : t + 1;
           if (XA) g2_load_raw(rec + (size_t)tn * tstride, gs, m, h, rawn);
           else loadA(tn, an);
           loadB(tn, 0, bn);
@@ -1528,22 +1397,17 @@ __global__ __launch_bounds__(256) void k_wgrad_b16(const float* __restrict__ rec
         if (b == 0) {
           if (XA) {
 #pragma unroll
-            for (int c = 0; c < 4; ++c) pin16(raw[XA ? c : 0]);
+            for (int c = 0; c < 4; ++c) pin(raw[XA ? c : 0]);
             g2_derive<MT>(raw, gw, m, av);
           } else {
 #pragma unroll
-          for (int a = 0; a < MT; ++a) pin16(av[a]);
+            for (int a = 0; a < MT; ++a) pin(av[a]);
           }
           prepA(av, nl, a3);
         }
-        pin16(bv);
+        pin(bv);
         if (nl < 32) mask_tail(bv, h, nl);  // never-written record slots may hold anything, 0 * NaN is NaN
-        const B3 b0 = split8(bv), b1 = split8(bv + 8);
-#pragma unroll
-        for (int a = 0; a < MT; ++a) {
-          acc[a][b] = mfma6(a3[a][0], b0, acc[a][b]);
-          acc[a][b] = mfma6(a3[a][1], b1, acc[a][b]);
-        }
+        product(b, bv);
 #pragma unroll
         for (int q = 0; q < 16; ++q) bv[q] = bn[q];
       }
@@ -1554,9 +1418,9 @@ __global__ __launch_bounds__(256) void k_wgrad_b16(const float* __restrict__ rec
           for (int q = 0; q < 16; ++q) raw[XA ? c : 0][q] = rawn[XA ? c : 0][q];
       } else {
 #pragma unroll
-      for (int a = 0; a < MT; ++a)
+        for (int a = 0; a < MT; ++a)
 #pragma unroll
-        for (int q = 0; q < 16; ++q) av[a][q] = an[a][q];
+          for (int q = 0; q < 16; ++q) av[a][q] = an[a][q];
       }
     }
   } else {
@@ -1571,14 +1435,14 @@ __global__ __launch_bounds__(256) void k_wgrad_b16(const float* __restrict__ rec
     }
     for (int t = t_begin; t < t_end; ++t) {
       const int nl = min(32, n - t * 32);
-      {
-        const int tn = min(t + 1, t_end - 1);  // (unconditionally, see above)
+      if (B16 || t + 1 < t_end) {  // (B16: unconditionally, see above)
+        const int tn = B16 ? min(t + 1, t_end - 1) : t + 1;
         loadA(tn, an);
         load_row_half(rec + (size_t)tn * tstride + (size_t)srow * 32, live, h, xn);
       }
-      pin16(x);
+      pin(x);
 #pragma unroll
-      for (int a = 0; a < MT; ++a) pin16(av[a]);
+      for (int a = 0; a < MT; ++a) pin(av[a]);
       if (nl < 32) mask_tail(x, h, nl);  // never-written record slots may hold anything, 0 * NaN is NaN
       prepA(av, nl, a3);
       float sn[16], cs[16];
@@ -1590,12 +1454,7 @@ __global__ __launch_bounds__(256) void k_wgrad_b16(const float* __restrict__ rec
         // the A operand is zero past nl, so the (finite) encoding of a padding sample never contributes
 #pragma unroll
         for (int q = 0; q < 16; ++q) bv[q] = live ? pe_pick<XF>(b, x[q], sn[q], cs[q], m0, m1) : 0.f;
-        const B3 b0 = split8(bv), b1 = split8(bv + 8);
-#pragma unroll
-        for (int a = 0; a < MT; ++a) {
-          acc[a][b] = mfma6(a3[a][0], b0, acc[a][b]);
-          acc[a][b] = mfma6(a3[a][1], b1, acc[a][b]);
-        }
+        product(b, bv);
       }
 #pragma unroll
       for (int q = 0; q < 16; ++q) x[q] = xn[q];
@@ -1702,7 +1561,7 @@ static int env_int(const char* name, int dflt) {
 static Knobs read_env_knobs() {
   Knobs k;
   // which stages run on the bf16 matrix cores with three-piece operands (fp32-level accuracy, jt_shade_core.h): bit 0 the
-  // forward chain (k_shade_fwd_b16), bit 1 the weight-gradient GEMMs (k_wgrad_b16), bit 2 the chain of the SPLIT backward
+  // forward chain (k_shade_fwd_b16), bit 1 the weight-gradient GEMMs (k_wgrad<.., true>), bit 2 the chain of the SPLIT backward
   // (k_shade_bwd<..., SPLIT, B16>).  JT_BF16X3 overrides the build default; 0 = everything on the fp32 matrix cores.
   k.matrix_mode = env_int("JT_BF16X3", JT_BF16X3_DEFAULT) & 7;
   k.split = env_int("JT_BWD_SPLIT", -1);
@@ -1751,6 +1610,11 @@ static int shade_kind(const JtScene* s) {
   if (s->n_comp_app == 20 && s->app_dim == 20 && s->mlp_hidden == 32 && s->mlp_kind == JT_MLP_WEAKVIEW) return 1;
   return -1;
 }
+// f(tag) with decltype(tag)::Cfg the configuration of scene kind `kind` (a shade_kind() that is not -1)
+template <class C>
+struct KindTag { typedef C Cfg; };
+template <class F>
+static auto for_kind(int kind, F&& f) { return kind == 0 ? f(KindTag<CfgBlender>()) : f(KindTag<CfgLlff>()); }
 
 #if JT_STAMP
 extern "C" int jt_debug_read_stamps(unsigned long long* out8) {
@@ -1861,7 +1725,7 @@ extern "C" size_t jt_shade_workspace_bytes(const JtScene* scene, int n_entries_m
   const int kind = shade_kind(scene);
   if (kind < 0 || n_entries_max < 1 || n_entries_max > kMaxEntries) return 0;
   const Knobs k = knobs();
-  return (kind == 0) ? WsLayout<CfgBlender>(k).bytes(n_entries_max) : WsLayout<CfgLlff>(k).bytes(n_entries_max);
+  return for_kind(kind, [&](auto tag) { return WsLayout<typename decltype(tag)::Cfg>(k).bytes(n_entries_max); });
 }
 
 // Where the pieces of a shade workspace sit, for the library's CURRENT modes (tests/test_sanitizers.py: every carved piece must
@@ -1900,8 +1764,7 @@ extern "C" int jt_shade_workspace_layout(const JtScene* scene, int n_entries_max
   const int kind = shade_kind(scene);
   if (kind < 0 || !out23) return JT_ERR_UNSUPPORTED;
   if (n_entries_max < 1 || n_entries_max > kMaxEntries) return JT_ERR_ARG;
-  if (kind == 0) ws_layout<CfgBlender>(n_entries_max, out23);
-  else ws_layout<CfgLlff>(n_entries_max, out23);
+  for_kind(kind, [&](auto tag) { ws_layout<typename decltype(tag)::Cfg>(n_entries_max, out23); });
   return JT_OK;
 }
 
@@ -1913,40 +1776,39 @@ extern "C" int jt_shade_record_layout(const JtScene* scene, int32_t* out) {
   const int kind = shade_kind(scene);
   if (kind < 0 || !out) return JT_ERR_UNSUPPORTED;
   const Knobs k = knobs();
-  if (kind == 0) {
-    out[0] = shade_tape<CfgBlender>(k).rows; out[1] = BwdCfg<CfgBlender>::R_MASK; out[2] = CfgBlender::HID;
-  } else {
-    out[0] = shade_tape<CfgLlff>(k).rows; out[1] = BwdCfg<CfgLlff>::R_MASK; out[2] = CfgLlff::HID;
-  }
+  for_kind(kind, [&](auto tag) {
+    typedef typename decltype(tag)::Cfg C;
+    out[0] = shade_tape<C>(k).rows, out[1] = BwdCfg<C>::R_MASK, out[2] = C::HID;
+  });
   out[3] = 32;
   return JT_OK;
 }
 
+struct ShadeFwdArgs {
+  const Dev& D;
+  const MlpDev& M;
+  const PeMask& pm;
+  const float *rays_o, *rays_d, *jitter, *zvals, *tmin, *vdir;
+  const int32_t *offset, *eray, *esmp;
+  int R, cap;
+  float* rgb_s;
+  hipStream_t st;
+};
 template <class C, int REC>
-static int launch_shade_fwd_t(const Dev& D, const MlpDev& M, const PeMask& pm, const float* rays_o,
-                              const float* rays_d, const float* jitter, const float* zvals, const float* tmin,
-                              const int32_t* offset, int R, const int32_t* eray, const int32_t* esmp,
-                              const float* vdir, float* rgb_s, float* rec, int cap, const Knobs& k, hipStream_t st) {
-  long tiles = ((long)cap + 31) / 32;
+static int launch_shade_fwd_t(const ShadeFwdArgs& a, float* rec, const Knobs& k) {
+  const long tiles = ((long)a.cap + 31) / 32;
   const int rows = shade_tape<C>(k).rows;
-  // matrix-mode bit 0: the forward's matrix stages as six bf16 MFMAs per fp32 product sum (jt_shade_core.h)
-  if (k.matrix_mode & 1) {
-    const size_t lds16 = B16Cfg<C>::LDS_BYTES;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_shade_fwd_b16<C, REC>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16);
-    constexpr int NW = JT_B16_THREADS / 64;
-    int blocks16 = (int)std::min<long>((tiles + NW - 1) / NW, chip().cus);   // one 115 KB-LDS workgroup per CU
-    hipLaunchKernelGGL((k_shade_fwd_b16<C, REC>), dim3(blocks16), dim3(JT_B16_THREADS), lds16, st, D, M, pm, rays_o, rays_d, jitter,
-                       zvals, tmin, offset, R, eray, esmp, vdir, rgb_s, rec, cap, rows);
-    JT_LAUNCH_CHECK();
-    return JT_OK;
-  }
-  const size_t lds = C::LDS_FLOATS * sizeof(float);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_shade_fwd<C, REC>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  int blocks = (int)std::min<long>((tiles + 3) / 4, 512);
-  hipLaunchKernelGGL((k_shade_fwd<C, REC>), dim3(blocks), dim3(256), lds, st, D, M, pm, rays_o, rays_d, jitter, zvals,
-                     tmin, offset, R, eray, esmp, vdir, rgb_s, rec, cap, rows);
+  auto launch = [&](auto kernel, long blocks, int threads, size_t lds) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(kernel, dim3((int)blocks), dim3(threads), lds, a.st, a.D, a.M, a.pm, a.rays_o, a.rays_d, a.jitter, a.zvals,
+                       a.tmin, a.offset, a.R, a.eray, a.esmp, a.vdir, a.rgb_s, rec, a.cap, rows);
+  };
+  constexpr int NW = JT_B16_THREADS / 64;
+  // matrix-mode bit 0: the forward's matrix stages as six bf16 MFMAs per fp32 product sum (jt_shade_core.h), one 115 KB-LDS
+  // workgroup per CU
+  if (k.matrix_mode & 1)
+    launch(k_shade_fwd_b16<C, REC>, std::min<long>((tiles + NW - 1) / NW, chip().cus), JT_B16_THREADS, B16Cfg<C>::LDS_BYTES);
+  else launch(k_shade_fwd<C, REC>, std::min<long>((tiles + 3) / 4, 512), 256, C::LDS_FLOATS * sizeof(float));
   JT_LAUNCH_CHECK();
   return JT_OK;
 }
@@ -1954,25 +1816,15 @@ static int launch_shade_fwd_t(const Dev& D, const MlpDev& M, const PeMask& pm, c
 // workspace != NULL: training forward, the records of the layer inputs are left in the workspace for
 // jt_shade_backward (which must be given the same workspace, untouched in between)
 template <class C>
-static int launch_shade_fwd(const Dev& D, const MlpDev& M, const PeMask& pm, const float* rays_o,
-                            const float* rays_d, const float* jitter, const float* zvals, const float* tmin,
-                            const int32_t* offset, int R, const int32_t* eray, const int32_t* esmp,
-                            const float* vdir, float* rgb_s, int cap, float* ws, size_t ws_bytes, int flags,
-                            hipStream_t st) {
+static int launch_shade_fwd(const ShadeFwdArgs& a, float* ws, size_t ws_bytes, int flags) {
   const Knobs k = knobs();
-  if (ws) {
-    if (ws_bytes < WsLayout<C>(k).bytes(cap)) return JT_ERR_ARG;
-    if (flags & JT_SHADE_POSE_ONLY)
-      return launch_shade_fwd_t<C, 2>(D, M, pm, rays_o, rays_d, jitter, zvals, tmin, offset, R, eray, esmp, vdir,
-                                      rgb_s, ws, cap, k, st);
-    if (shade_tape<C>(k).lean)
-      return launch_shade_fwd_t<C, 3>(D, M, pm, rays_o, rays_d, jitter, zvals, tmin, offset, R, eray, esmp, vdir,
-                                      rgb_s, ws, cap, k, st);
-    return launch_shade_fwd_t<C, 1>(D, M, pm, rays_o, rays_d, jitter, zvals, tmin, offset, R, eray, esmp, vdir,
-                                    rgb_s, ws, cap, k, st);
-  }
-  return launch_shade_fwd_t<C, 0>(D, M, pm, rays_o, rays_d, jitter, zvals, tmin, offset, R, eray, esmp, vdir,
-                                  rgb_s, nullptr, cap, k, st);
+  if (ws && ws_bytes < WsLayout<C>(k).bytes(a.cap)) return JT_ERR_ARG;
+  // the record set: none, pose-only, lean tape, full tape
+  const auto launch = !ws                           ? &launch_shade_fwd_t<C, 0>
+                      : (flags & JT_SHADE_POSE_ONLY) ? &launch_shade_fwd_t<C, 2>
+                      : shade_tape<C>(k).lean        ? &launch_shade_fwd_t<C, 3>
+                                                     : &launch_shade_fwd_t<C, 1>;
+  return launch(a, ws, k);
 }
 
 extern "C" int jt_shade_forward(const JtScene* scene, const JtFactors* factors, const JtMlp* mlp, const float* rays_o,
@@ -1994,14 +1846,11 @@ extern "C" int jt_shade_forward(const JtScene* scene, const JtFactors* factors, 
   if (n_entries_max > kMaxEntries) return JT_ERR_ARG;
   MlpDev M = {mlp->basis, mlp->w1, mlp->b1, mlp->w2, mlp->b2, mlp->w3, mlp->b3};
   PeMask pm = pe_masks(scene->fea_pe_progress, scene->view_pe_progress, scene->fea_pe, scene->view_pe);
-  hipStream_t st = (hipStream_t)stream;
-  if (kind == 0)
-    return launch_shade_fwd<CfgBlender>(D, M, pm, rays_o, rays_d, jitter, zvals, tmin, shade_offset, n_rays,
-                                        entry_ray, entry_smp, viewdirs, rgb_s, n_entries_max, (float*)workspace,
-                                        workspace_bytes, flags, st);
-  return launch_shade_fwd<CfgLlff>(D, M, pm, rays_o, rays_d, jitter, zvals, tmin, shade_offset, n_rays, entry_ray,
-                                   entry_smp, viewdirs, rgb_s, n_entries_max, (float*)workspace, workspace_bytes, flags,
-                                   st);
+  const ShadeFwdArgs a = {D, M, pm, rays_o, rays_d, jitter, zvals, tmin, viewdirs, shade_offset, entry_ray, entry_smp, n_rays,
+                          n_entries_max, rgb_s, (hipStream_t)stream};
+  return for_kind(kind, [&](auto tag) {
+    return launch_shade_fwd<typename decltype(tag)::Cfg>(a, (float*)workspace, workspace_bytes, flags);
+  });
 }
 
 // the tile-owned scatter (jt_tile.h) per scene kind.  Configuration 1 (the default): ONE channel class, eight-wave workgroups
@@ -2188,15 +2037,29 @@ static ShadeBwdPlan plan_shade_bwd(const Knobs& k, const Chip& chip, const Shade
 
 // ---- launch code: one function template per kernel family, executing a plan ------------------------------------------------------
 // each sets the dynamic-LDS attribute of its instantiation once and launches; the caller checks hipGetLastError
-template <class C, bool DET, bool SPLIT, bool B16, class... Args>
-static void launch_chain(int blocks, size_t lds, hipStream_t st, Args... args) {
+struct ChainArgs {
+  const Dev& D;
+  const MlpDev& M;
+  const PeMask& pm;
+  const JtFactors& G;
+  const int32_t* offset;
+  const float *rgb_s, *g_rgb_s;
+  float *g_xyz, *rec;
+  unsigned* bad;
+  int R, start, ccap, cap, ablate, rec_rows, blocks;
+  size_t lds;
+  hipStream_t st;
+};
+template <class C, bool DET, bool SPLIT, bool B16>
+static void launch_chain(const ChainArgs& a) {
   static bool attr = false;
   if (!attr) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_shade_bwd<C, DET, SPLIT, B16>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.lds);
     attr = true;
   }
-  hipLaunchKernelGGL((k_shade_bwd<C, DET, SPLIT, B16>), dim3(blocks), dim3(512), lds, st, args...);
+  hipLaunchKernelGGL((k_shade_bwd<C, DET, SPLIT, B16>), dim3(a.blocks), dim3(512), a.lds, a.st, a.D, a.M, a.pm, a.G, a.offset, a.R,
+                     a.rgb_s, a.g_rgb_s, a.g_xyz, a.rec, a.start, a.ccap, a.cap, a.ablate, a.bad, a.rec_rows);
 }
 
 struct ScatterArgs {
@@ -2286,8 +2149,7 @@ static void launch_pose_gather(int blocks, hipStream_t st, Args... args) {
 
 template <bool B16, int MT, int NT, int XF, int XA, class... Args>
 static void launch_wgrad_gemm(hipStream_t st, Args... args) {
-  if constexpr (B16) hipLaunchKernelGGL((k_wgrad_b16<MT, NT, XF, XA>), dim3(kWgradBlocks), dim3(256), 0, st, args...);
-  else hipLaunchKernelGGL((k_wgrad<MT, NT, XF, XA>), dim3(kWgradBlocks), dim3(256), 0, st, args...);
+  hipLaunchKernelGGL((k_wgrad<MT, NT, XF, XA, B16>), dim3(kWgradBlocks), dim3(256), 0, st, args...);
 }
 // the weight-gradient GEMMs of one chunk: dW3/db3 = GO^T MID ; dW2/db2 = G2^T H1 ; dW1/db1 = G1^T X(F, d) ; dBasis = GF^T PROD
 // (the last one only where dBasis does not come out of the scatter)
@@ -2355,23 +2217,13 @@ static int launch_shade_bwd(const ShadeBwdPlan& P, const Knobs& k, const Dev& D,
     long tiles = ((long)ccap + 31) / 32;
     int blocks = (int)std::min<long>((tiles + B::NWAVE - 1) / B::NWAVE, chip().cus);   // one workgroup per CU (its LDS fills it)
     float* rc = recs + W.rec_floats_per_chunk() * ci;
-    const size_t lds = (size_t)P.chain_lds;
+    const ChainArgs a = {D, M, pm, G, offset, rgb_s, g_rgb_s, g_xyz, rc, bad, R, start, ccap, cap, ablate, RR, blocks,
+                         (size_t)P.chain_lds, st};
     switch (P.chain) {
-      case kChainSplitB16:
-        launch_chain<C, false, true, true>(blocks, lds, st, D, M, pm, G, offset, R, rgb_s, g_rgb_s, g_xyz, rc, start, ccap, cap,
-                                           ablate, bad, RR);
-        break;
-      case kChainSplit:
-        launch_chain<C, false, true, false>(blocks, lds, st, D, M, pm, G, offset, R, rgb_s, g_rgb_s, g_xyz, rc, start, ccap, cap,
-                                            ablate, bad, RR);
-        break;
-      case kChainFusedDet:
-        launch_chain<C, true, false, false>(blocks, lds, st, D, M, pm, G, offset, R, rgb_s, g_rgb_s, g_xyz, rc, start, ccap, cap,
-                                            ablate, bad, RR);
-        break;
-      default:
-        launch_chain<C, false, false, false>(blocks, lds, st, D, M, pm, G, offset, R, rgb_s, g_rgb_s, g_xyz, rc, start, ccap, cap,
-                                             ablate, bad, RR);
+      case kChainSplitB16: launch_chain<C, false, true, true>(a); break;
+      case kChainSplit: launch_chain<C, false, true, false>(a); break;
+      case kChainFusedDet: launch_chain<C, true, false, false>(a); break;
+      default: launch_chain<C, false, false, false>(a);
     }
     JT_LAUNCH_CHECK();
     return JT_OK;
@@ -2403,8 +2255,7 @@ static int launch_shade_bwd(const ShadeBwdPlan& P, const Knobs& k, const Dev& D,
     const int start = ci * chunk, ccap = std::min(chunk, cap - start);
     const float* rec = recs + W.rec_floats_per_chunk() * ci;
     float* s = slabs + (size_t)ci * cstride;
-    return P.gemm_b16 ? launch_wgrad<C, true>(P, M, pm, rec, offset, R, cap, start, ccap, s, ws_st)
-                      : launch_wgrad<C, false>(P, M, pm, rec, offset, R, cap, start, ccap, s, ws_st);
+    return (P.gemm_b16 ? launch_wgrad<C, true> : launch_wgrad<C, false>)(P, M, pm, rec, offset, R, cap, start, ccap, s, ws_st);
   };
   const bool pipe = P.gemm_pipe;
   for (int ci = 0; ci < nchunks; ++ci) {
@@ -2474,9 +2325,9 @@ extern "C" int jt_shade_backward_plan(const JtScene* scene, int want_factor_grad
   for (int a = 0; a < 3; ++a)
     if (scene->plane_h[a] < 1 || scene->plane_w[a] < 1 || scene->line_len[a] < 1) return JT_ERR_ARG;
   const ShadeBwdInputs in = shade_bwd_inputs(scene, want_factor_grads != 0, want_mlp_grads != 0, flags, have_aux != 0);
-  const ShadeBwdPlan P = kind == 0 ? plan_shade_bwd<CfgBlender>(knobs(), chip(), in) : plan_shade_bwd<CfgLlff>(knobs(), chip(), in);
+  const ShadeBwdPlan P = for_kind(kind, [&](auto tag) { return plan_shade_bwd<typename decltype(tag)::Cfg>(knobs(), chip(), in); });
   if (P.status) return P.status;
-  if (P.second == kSecondScatter && !(kind == 0 ? find_scatter<CfgBlender>(P) : find_scatter<CfgLlff>(P)))
+  if (P.second == kSecondScatter && !for_kind(kind, [&](auto tag) { return find_scatter<typename decltype(tag)::Cfg>(P); }))
     return JT_ERR_UNSUPPORTED;
   const int32_t v[16] = {P.split_requested, P.split, P.chain, P.second, P.sc_det, P.sc_run, P.sc_waves, P.sc_flags,
                          P.sc_lds, P.sc_wgs, P.lean, P.rec_rows, P.dbasis_in_scatter, P.gemm_b16, P.gemm_count, P.gemm_forked};
@@ -2518,11 +2369,10 @@ extern "C" int jt_shade_backward(const JtScene* scene, const JtFactors* factors,
   const Knobs k = knobs();
   const ShadeBwdInputs in = shade_bwd_inputs(scene, g_factors != nullptr, g_mlp != nullptr, flags,
                                              aux_stream && ev_fork && ev_join);
-  if (kind == 0)
-    return launch_shade_bwd<CfgBlender>(plan_shade_bwd<CfgBlender>(k, chip(), in), k, D, M, pm, GFr, GMr, shade_offset, n_rays,
-                                        rgb_s, g_rgb_s, g_xyz_app, n_entries_max, (float*)workspace, workspace_bytes, st,
-                                        (hipStream_t)aux_stream, (hipEvent_t)ev_fork, (hipEvent_t)ev_join);
-  return launch_shade_bwd<CfgLlff>(plan_shade_bwd<CfgLlff>(k, chip(), in), k, D, M, pm, GFr, GMr, shade_offset, n_rays, rgb_s,
-                                   g_rgb_s, g_xyz_app, n_entries_max, (float*)workspace, workspace_bytes, st,
-                                   (hipStream_t)aux_stream, (hipEvent_t)ev_fork, (hipEvent_t)ev_join);
+  return for_kind(kind, [&](auto tag) {
+    typedef typename decltype(tag)::Cfg C;
+    return launch_shade_bwd<C>(plan_shade_bwd<C>(k, chip(), in), k, D, M, pm, GFr, GMr, shade_offset, n_rays, rgb_s, g_rgb_s,
+                               g_xyz_app, n_entries_max, (float*)workspace, workspace_bytes, st, (hipStream_t)aux_stream,
+                               (hipEvent_t)ev_fork, (hipEvent_t)ev_join);
+  });
 }
