@@ -133,18 +133,10 @@ JT_FUSED_FN void fused_tile_fwd(const Dev& D, const FusedArgs& A, const PeMask& 
   for (int rr = 0; rr < 16; ++rr) tb[(rowmap(rr, 0) + 4 * h) * 32 + j] = facc[rr];
   Hidden<C> h1 = layer1<C>(smem, facc, o.vd, pm, j, h);
   relu_<C>(h1);
-  unsigned mask1 = 0u;
-#pragma unroll
-  for (int mt = 0; mt < C::MT; ++mt)
-#pragma unroll
-    for (int rr = 0; rr < 16; ++rr) mask1 |= (h1.v[mt][rr] > 0.f) ? (1u << (mt * 16 + rr)) : 0u;
+  const unsigned mask1 = relu_signs<C>(h1);
   Hidden<C> h2 = layer2<C>(smem, h1, j, h);
   relu_<C>(h2);
-  unsigned mask2 = 0u;
-#pragma unroll
-  for (int mt = 0; mt < C::MT; ++mt)
-#pragma unroll
-    for (int rr = 0; rr < 16; ++rr) mask2 |= (h2.v[mt][rr] > 0.f) ? (1u << (mt * 16 + rr)) : 0u;
+  const unsigned mask2 = relu_signs<C>(h2);
   tb[(kRowMask + h) * 32 + j] = __uint_as_float(mask1);
   tb[(kRowMask + 2 + h) * 32 + j] = __uint_as_float(mask2);
   float out[3];

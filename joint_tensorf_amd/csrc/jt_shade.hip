@@ -38,230 +38,183 @@ namespace jt {
 // as 1 without the 3 Ca product rows -- dBasis is then formed inside k_shade_scatter from the plane x line products the
 // walkers hold anyway, and a tile's record block is `rrows` = R_LEAN rows instead of REC_FLOATS (1 088 instead of 1 920 bytes
 // per shaded sample for VM-48).  `rrows` is a launch argument in every kernel that addresses records.
-template <class C, int REC>
-__global__ __launch_bounds__(256, 2) void k_shade_fwd(Dev D, MlpDev M, PeMask pm, const float* __restrict__ rays_o,
-                                                      const float* __restrict__ rays_d,
-                                                      const float* __restrict__ jitter,
-                                                      const float* __restrict__ zvals,
-                                                      const float* __restrict__ tmin,
-                                                      const int* __restrict__ offset, int R,
-                                                      const int* __restrict__ eray, const int* __restrict__ esmp,
-                                                      const float* __restrict__ vdir, float* __restrict__ rgb_s,
-                                                      float* __restrict__ rec, int cap, int rrows) {
+//
+// B16: the three matrix stages on the bf16 matrix cores at fp32-level accuracy (jt_shade_core.h, "bf16x3"), one workgroup of
+// eight waves per CU around a 114 KB pre-split weight image; otherwise on the fp32 matrix cores, four waves around the 75 KB
+// fp32 image.  Selected by matrix-mode bit 0 (launch_shade_fwd_t); everything but the three stages is common to both.
+
+// launch shape of k_shade_fwd<.., B16>: the kernel and launch_shade_fwd_t take it from here
+template <bool B16>
+struct FwdShape {
+  static constexpr int THREADS = B16 ? JT_B16_THREADS : 256;
+  static constexpr int NW = THREADS / 64;  // waves of a workgroup, one tile each at a time
+  template <class C>
+  static constexpr size_t lds_bytes() { return B16 ? B16Cfg<C>::LDS_BYTES : C::LDS_FLOATS * sizeof(float); }
+  // most workgroups of a launch: one per CU on the bf16 path (its 115 KB image fills the CU's LDS), 512 of the fp32 ones
+  static long grid_cap() { return B16 ? chip().cus : 512; }
+};
+
+// the workgroup's weight image as the stages read it.  fp32: `smem` is the image (load_weights_lds).  bf16: `img` the pre-split
+// vectors, `tail` the fp32 tail behind them (load_weights_lds_b16), and `smem` = tail - C::O_W3, because layer3 reads W3 / b3 at
+// their fp32-image offsets and the tail keeps that relative layout.
+// The steps take it BY VALUE.  By reference -- the same LDS instructions, another register allocation -- the fp32 VM-48 kernels
+// went from 219 (REC 0) and 241 (REC 1-3) VGPRs to 253 and to 256 with 8 bytes of scratch per lane; by value they take 221 and
+// 241 / 245 and no scratch (the other twelve instantiations do not care).
+struct FwdLds {
+  const uint4* img;
+  const float* tail;
+  const float* smem;
+};
+// the arrays of a launch (the kernel's arguments) and the shaded-sample count
+struct FwdIo {
+  const float *rays_o, *rays_d, *jitter, *zvals, *tmin;
+  const int *eray, *esmp;
+  const float* vdir;
+  float *rgb_s, *rec;
+  int total, rrows;
+};
+// what the gather step of a tile leaves for its compute step
+struct FwdTile {
+  f32x16 facc;         // basis_mat output
+  float vd0, vd1, vd2;  // view direction (scalars: as an array, state that outlives a step ends up in scratch memory)
+  float* rt;           // the tile's record block
+  int e;               // the lane's entry
+  bool on;             // ... exists
+};
+
+// A tile is a GATHER step (taps, products, basis product: half of a wave's time, most of it waiting for the texture path)
+// and a COMPUTE step (encodings, layers, records: vector and matrix instructions).  Between them they write the whole tape:
+// every record row the backward kernels read is stored here and nowhere else.
+// (force-inlined functions, not lambdas: captured by reference, the 20-channel bf16 instantiation kept 192 bytes of its state
+//  in scratch memory and its forward went from 0.117 to 0.144 ms)
+template <class C, int REC, bool B16>
+__device__ __forceinline__ void fwd_gather_step(const Dev& D, const FwdLds L, const FwdIo& A, int tile, int j_, int h_,
+                                                int lane, FwdTile& t) {
   typedef BwdCfg<C> B;
-  extern __shared__ __align__(16) float smem[];
-  const int total = min(offset[R], cap);
-  const int ntiles = (total + 31) >> 5;
-  const int nblk = min((int)gridDim.x, (ntiles + 3) / 4);  // the grid is sized for the worst case
-  if ((int)blockIdx.x >= nblk) return;
-  load_weights_lds<C>(smem, M);
-  __syncthreads();
-  // (the wave index as a scalar: everything derived from it -- tile, record block -- stays in scalar registers)
-  const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int j_ = lane & 31, h_ = lane >> 5;
+  int j = j_, h = h_;  // see k_shade_bwd: keeps per-lane address math from being hoisted out of the loop
+  asm volatile("" : "+v"(j), "+v"(h));
+  t.e = tile * 32 + j;
+  t.on = t.e < A.total;
+  const int ee = t.on ? t.e : A.total - 1;
+  t.rt = REC ? A.rec + (size_t)tile * (size_t)A.rrows * 32 : nullptr;
+  EntryGeom g = entry_geom(D, A.rays_o, A.rays_d, A.jitter, A.zvals, A.tmin, A.eray, A.esmp, ee);
+  t.vd0 = A.vdir[(size_t)ee * 3], t.vd1 = A.vdir[(size_t)ee * 3 + 1], t.vd2 = A.vdir[(size_t)ee * 3 + 2];
+  const float vd[3] = {t.vd0, t.vd1, t.vd2};
+  if (REC && t.on && h == 0) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      if (REC & 1) rec_st(rec_at(t.rt, B::R_VD + c, 4u * (unsigned)j), vd[c]);
+      rec_st(rec_at(t.rt, B::R_GEO + c, 4u * (unsigned)j), g.n[c]);
+    }
+  }
+  if constexpr (B16) t.facc = gather_basis_b16<C, REC == 1>(D, L.img, g.n, j, h, lane, t.rt, t.on);
+  else t.facc = gather_basis<C, REC == 1>(D, L.smem, g.n, j, h, t.rt, t.on);
+  if (REC) rec_store<1>(t.rt, B::R_F, &t.facc, j, h, t.on);
+}
+
+template <class C, int REC, bool B16>
+__device__ __forceinline__ void fwd_compute_step(const FwdLds L, const FwdIo& A, const PeMask& pm, int j_, int h_, int lane,
+                                                 const FwdTile& t) {
+  typedef BwdCfg<C> B;
   constexpr int HOFF = (C::KIND == JT_MLP_FEA) ? 0 : 12;
-  const XcdShare xs = xcd_share(ntiles, nblk);  // tiles of neighbouring samples meet in one XCD's L2
-  for (int tile = xs.lo + xs.rank * 4 + wv; tile < xs.hi; tile += xs.peers * 4) {
-    int j = j_, h = h_;  // see k_shade_bwd: keeps per-lane address math from being hoisted out of the loop
-    asm volatile("" : "+v"(j), "+v"(h));
-    const int e = tile * 32 + j;
-    const bool on = e < total;
-    const int ee = on ? e : total - 1;
-    float* rt = REC ? rec + (size_t)tile * (size_t)rrows * 32 : nullptr;
-    EntryGeom g = entry_geom(D, rays_o, rays_d, jitter, zvals, tmin, eray, esmp, ee);
-    float vd[3] = {vdir[(size_t)ee * 3], vdir[(size_t)ee * 3 + 1], vdir[(size_t)ee * 3 + 2]};
-    if (REC && on && h == 0) {
+  int j = j_, h = h_;
+  asm volatile("" : "+v"(j), "+v"(h));
+  const float vd[3] = {t.vd0, t.vd1, t.vd2};
+  Hidden<C> h1;
+  if constexpr (B16) h1 = layer1_b16<C>(L.img, L.tail, t.facc, vd, pm, h, lane);
+  else h1 = layer1<C>(L.smem, t.facc, vd, pm, j, h);
+  relu_<C>(h1);
+  if (REC) {
+    const unsigned mask1 = relu_signs<C>(h1);
+    if (t.on) rec_st(rec_at(t.rt, B::R_MASK, 4u * (unsigned)j + 128u * (unsigned)h), __uint_as_float(mask1));
+    if (REC & 1) rec_store<C::MT>(t.rt, B::R_H1, h1.v, j, h, t.on);
+  }
+  Hidden<C> h2;
+  if constexpr (B16) h2 = layer2_b16<C>(L.img, L.tail, h1, h, lane);
+  else h2 = layer2<C>(L.smem, h1, j, h);
+  relu_<C>(h2);
+  if (REC) {
+    const unsigned mask2 = relu_signs<C>(h2);
+    if (t.on) rec_st(rec_at(t.rt, B::R_MASK + 2, 4u * (unsigned)j + 128u * (unsigned)h), __uint_as_float(mask2));
+    if (REC & 1) rec_store<C::MT>(t.rt, B::R_MID + HOFF, h2.v, j, h, t.on);
+    if ((REC & 1) && C::KIND != JT_MLP_FEA) {
+      float pe[12];
+      view_pe(vd, pm, pe);
+      if (t.on && h == 0) {
 #pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        if (REC & 1) rec_st(rec_at(rt, B::R_VD + c, 4u * (unsigned)j), vd[c]);
-        rec_st(rec_at(rt, B::R_GEO + c, 4u * (unsigned)j), g.n[c]);
+        for (int k = 0; k < 12; ++k) rec_st(rec_at(t.rt, B::R_MID + k, 4u * (unsigned)j), pe[k]);
       }
     }
-    f32x16 facc = gather_basis<C, REC == 1>(D, smem, g.n, j, h, rt, on);
-    if (REC) rec_store<1>(rt, B::R_F, &facc, j, h, on);
-    Hidden<C> h1 = layer1<C>(smem, facc, vd, pm, j, h);
-    relu_<C>(h1);
-    if (REC) {
-      unsigned mask1 = 0u;
+  }
+  float o[3];
+  layer3<C>(L.smem, h2, vd, pm, h, o);
+  if (t.on && h == 0) {
 #pragma unroll
-      for (int mt = 0; mt < C::MT; ++mt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) mask1 |= (h1.v[mt][r] > 0.f) ? (1u << (mt * 16 + r)) : 0u;
-      if (on) rec_st(rec_at(rt, B::R_MASK, 4u * (unsigned)j + 128u * (unsigned)h), __uint_as_float(mask1));
-      if (REC & 1) rec_store<C::MT>(rt, B::R_H1, h1.v, j, h, on);
-    }
-    Hidden<C> h2 = layer2<C>(smem, h1, j, h);
-    relu_<C>(h2);
-    if (REC) {
-      unsigned mask2 = 0u;
-#pragma unroll
-      for (int mt = 0; mt < C::MT; ++mt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) mask2 |= (h2.v[mt][r] > 0.f) ? (1u << (mt * 16 + r)) : 0u;
-      if (on) rec_st(rec_at(rt, B::R_MASK + 2, 4u * (unsigned)j + 128u * (unsigned)h), __uint_as_float(mask2));
-      if (REC & 1) rec_store<C::MT>(rt, B::R_MID + HOFF, h2.v, j, h, on);
-      if ((REC & 1) && C::KIND != JT_MLP_FEA) {
-        float pe[12];
-        view_pe(vd, pm, pe);
-        if (on && h == 0) {
-#pragma unroll
-          for (int k = 0; k < 12; ++k) rec_st(rec_at(rt, B::R_MID + k, 4u * (unsigned)j), pe[k]);
-        }
-      }
-    }
-    float o[3];
-    layer3<C>(smem, h2, vd, pm, h, o);
-    if (on && h == 0) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) rgb_s[(size_t)e * 3 + c] = 1.f / (1.f + expf(-o[c]));
-    }
+    for (int c = 0; c < 3; ++c) A.rgb_s[(size_t)t.e * 3 + c] = 1.f / (1.f + expf(-o[c]));
   }
 }
 
-
-#if JT_STAMP
-// profiling build only (tools/build_variant.py -DJT_STAMP=1): cycles a wave of k_shade_fwd_b16 spends per phase of a tile,
-// summed over all waves and tiles; read and cleared by jt_debug_read_stamps (tools/stamp_fwd.py)
-__device__ unsigned long long g_stamps[8];
-#define JT_STAMP_T() (__builtin_readcyclecounter())
-#endif
-
-// The same forward with the three matrix stages on the bf16 matrix cores at fp32-level accuracy (jt_shade_core.h, "bf16x3"):
-// one workgroup of eight waves per CU around a 114 KB pre-split weight image.  Selected by JT_BF16X3 (launch_shade_fwd_t).
-template <class C, int REC>
-__global__ __launch_bounds__(JT_B16_THREADS) void k_shade_fwd_b16(Dev D, MlpDev M, PeMask pm, const float* __restrict__ rays_o,
-                                                      const float* __restrict__ rays_d,
-                                                      const float* __restrict__ jitter,
-                                                      const float* __restrict__ zvals,
-                                                      const float* __restrict__ tmin,
-                                                      const int* __restrict__ offset, int R,
-                                                      const int* __restrict__ eray, const int* __restrict__ esmp,
-                                                      const float* __restrict__ vdir, float* __restrict__ rgb_s,
-                                                      float* __restrict__ rec, int cap, int rrows) {
-  typedef BwdCfg<C> B;
+template <class C, int REC, bool B16>
+__global__ __launch_bounds__(FwdShape<B16>::THREADS, B16 ? 1 : 2) void k_shade_fwd(
+    Dev D, MlpDev M, PeMask pm, const float* __restrict__ rays_o, const float* __restrict__ rays_d,
+    const float* __restrict__ jitter, const float* __restrict__ zvals, const float* __restrict__ tmin,
+    const int* __restrict__ offset, int R, const int* __restrict__ eray, const int* __restrict__ esmp,
+    const float* __restrict__ vdir, float* __restrict__ rgb_s, float* __restrict__ rec, int cap, int rrows) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
-  typedef B16Cfg<C> Q;
-  const uint4* img = reinterpret_cast<const uint4*>(smem_raw);
-  const float* tail = reinterpret_cast<const float*>(smem_raw + (size_t)Q::V_END * 16);
-  const float* smem = tail - C::O_W3;  // layer3 reads W3 / b3 at their fp32-image offsets: the tail keeps that relative layout
+  constexpr int NW = FwdShape<B16>::NW;
   const int total = min(offset[R], cap);
   const int ntiles = (total + 31) >> 5;
-  constexpr int NW = JT_B16_THREADS / 64;
   const int nblk = min((int)gridDim.x, (ntiles + NW - 1) / NW);  // the grid is sized for the worst case
   if ((int)blockIdx.x >= nblk) return;
-  load_weights_lds_b16<C>(smem_raw, M);
+  FwdLds L;
+  if constexpr (B16) {
+    L.img = reinterpret_cast<const uint4*>(smem_raw);
+    L.tail = reinterpret_cast<const float*>(smem_raw + (size_t)B16Cfg<C>::V_END * 16);
+    L.smem = L.tail - C::O_W3;
+    load_weights_lds_b16<C>(smem_raw, M);
+  } else {
+    L.img = nullptr, L.tail = nullptr;
+    L.smem = reinterpret_cast<const float*>(smem_raw);
+    load_weights_lds<C>(reinterpret_cast<float*>(smem_raw), M);
+  }
   __syncthreads();
   // (the wave index as a scalar: everything derived from it -- tile, record block -- stays in scalar registers)
   const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int j_ = lane & 31, h_ = lane >> 5;
-  constexpr int HOFF = (C::KIND == JT_MLP_FEA) ? 0 : 12;
   const XcdShare xs = xcd_share(ntiles, nblk);  // tiles of neighbouring samples meet in one XCD's L2
-#if JT_SETPRIO
-  if (wv >= NW / 2) __builtin_amdgcn_s_setprio(1);  // static priority for the later-dispatched wave of every SIMD: measured, no effect
-#endif
-  // A tile is a GATHER step (taps, products, basis product: half of a wave's time, most of it waiting for the texture path)
-  // and a COMPUTE step (encodings, layers, records: vector and matrix instructions).  JT_B16_PINGPONG (inference only, below):
-  // the two waves of a SIMD (w and w + NW / 2) take the steps in opposite order with a workgroup barrier between steps, so
-  // that one of them computes while the other gathers instead of both queueing for the same unit.
+  const FwdIo A = {rays_o, rays_d, jitter, zvals, tmin, eray, esmp, vdir, rgb_s, rec, total, rrows};
   const int stride = xs.peers * NW;
   const int first = xs.lo + xs.rank * NW;
-  const int iters0 = first < xs.hi ? (xs.hi - first + stride - 1) / stride : 0;  // tiles of the workgroup's wave 0: uniform
-  f32x16 facc;
-  float vd0 = 0.f, vd1 = 0.f, vd2 = 0.f;  // (scalars: an array captured by reference below ends up in scratch memory)
-  int e = 0;
-  bool on = false, have = false;
-  float* rt = nullptr;
+  FwdTile t;
 #pragma unroll
-  for (int r = 0; r < 16; ++r) facc[r] = 0.f;
-  // (the two steps as macros, not lambdas: captured by reference, the 20-channel instantiation kept 192 bytes of its state in
-  //  scratch memory and its forward went from 0.117 to 0.144 ms)
-#define JT_FWD_GATHER_STEP \
-  {                                                                                                                    \
-    int j = j_, h = h_; \
-    asm volatile("" : "+v"(j), "+v"(h)); \
-    e = tile * 32 + j; \
-    on = e < total; \
-    const int ee = on ? e : total - 1; \
-    rt = REC ? rec + (size_t)tile * (size_t)rrows * 32 : nullptr; \
-    EntryGeom g = entry_geom(D, rays_o, rays_d, jitter, zvals, tmin, eray, esmp, ee); \
-    vd0 = vdir[(size_t)ee * 3], vd1 = vdir[(size_t)ee * 3 + 1], vd2 = vdir[(size_t)ee * 3 + 2]; \
-    const float vd[3] = {vd0, vd1, vd2}; \
-    if (REC && on && h == 0) { \
-_Pragma("unroll") \
-      for (int c = 0; c < 3; ++c) { \
-        if (REC & 1) rec_st(rec_at(rt, B::R_VD + c, 4u * (unsigned)j), vd[c]); \
-        rec_st(rec_at(rt, B::R_GEO + c, 4u * (unsigned)j), g.n[c]); \
-      } \
-    } \
-    facc = gather_basis_b16<C, REC == 1>(D, img, g.n, j, h, lane, rt, on); \
-    if (REC) rec_store<1>(rt, B::R_F, &facc, j, h, on); \
-  }
-#define JT_FWD_COMPUTE_STEP \
-  {                                                                                                                    \
-    int j = j_, h = h_; \
-    asm volatile("" : "+v"(j), "+v"(h)); \
-    const float vd[3] = {vd0, vd1, vd2}; \
-    Hidden<C> h1 = layer1_b16<C>(img, tail, facc, vd, pm, h, lane); \
-    relu_<C>(h1); \
-    if (REC) { \
-      unsigned mask1 = 0u; \
-_Pragma("unroll") \
-      for (int mt = 0; mt < C::MT; ++mt) \
-_Pragma("unroll") \
-        for (int r = 0; r < 16; ++r) mask1 |= (h1.v[mt][r] > 0.f) ? (1u << (mt * 16 + r)) : 0u; \
-      if (on) rec_st(rec_at(rt, B::R_MASK, 4u * (unsigned)j + 128u * (unsigned)h), __uint_as_float(mask1)); \
-      if (REC & 1) rec_store<C::MT>(rt, B::R_H1, h1.v, j, h, on); \
-    } \
-    Hidden<C> h2 = layer2_b16<C>(img, tail, h1, h, lane); \
-    relu_<C>(h2); \
-    if (REC) { \
-      unsigned mask2 = 0u; \
-_Pragma("unroll") \
-      for (int mt = 0; mt < C::MT; ++mt) \
-_Pragma("unroll") \
-        for (int r = 0; r < 16; ++r) mask2 |= (h2.v[mt][r] > 0.f) ? (1u << (mt * 16 + r)) : 0u; \
-      if (on) rec_st(rec_at(rt, B::R_MASK + 2, 4u * (unsigned)j + 128u * (unsigned)h), __uint_as_float(mask2)); \
-      if (REC & 1) rec_store<C::MT>(rt, B::R_MID + HOFF, h2.v, j, h, on); \
-      if ((REC & 1) && C::KIND != JT_MLP_FEA) { \
-        float pe[12]; \
-        view_pe(vd, pm, pe); \
-        if (on && h == 0) { \
-_Pragma("unroll") \
-          for (int k = 0; k < 12; ++k) rec_st(rec_at(rt, B::R_MID + k, 4u * (unsigned)j), pe[k]); \
-        } \
-      } \
-    } \
-    float o[3]; \
-    layer3<C>(smem, h2, vd, pm, h, o); \
-    if (on && h == 0) { \
-_Pragma("unroll") \
-      for (int c = 0; c < 3; ++c) rgb_s[(size_t)e * 3 + c] = 1.f / (1.f + expf(-o[c])); \
-    } \
-  }
-  // in lock step only where it pays: the inference forward of the 48-channel scene (800 x 800 eval render 168 -> 157 ms); the
+  for (int r = 0; r < 16; ++r) t.facc[r] = 0.f;
+  t.vd0 = t.vd1 = t.vd2 = 0.f, t.rt = nullptr, t.e = 0, t.on = false;
+  // JT_B16_PINGPONG: the two waves of a SIMD (w and w + NW / 2) take the steps in opposite order with a workgroup barrier
+  // between steps, so that one of them computes while the other gathers instead of both queueing for the same unit.
+  // In lock step only where it pays: the inference forward of the 48-channel scene (800 x 800 eval render 168 -> 157 ms); the
   // training forward is unchanged by it (0.485 / 0.479 ms) and the 20-channel one, whose gather step is short, loses
   // (0.117 -> 0.153 ms)
-  if (JT_B16_PINGPONG && REC == 0 && C::CA >= 48) {
+  if constexpr (B16 && JT_B16_PINGPONG && REC == 0 && C::CA >= 48) {
+    const int iters0 = first < xs.hi ? (xs.hi - first + stride - 1) / stride : 0;  // tiles of the workgroup's wave 0: uniform
     const int half = (wv >= NW / 2) ? 1 : 0;
+    bool have = false;
     for (int step = 0; step < 2 * iters0 + 1; ++step) {
       if ((step & 1) == half) {
         const int tile = first + wv + ((step - half) >> 1) * stride;
         have = tile < xs.hi;
-        if (have) JT_FWD_GATHER_STEP
+        if (have) fwd_gather_step<C, REC, B16>(D, L, A, tile, j_, h_, lane, t);
       } else if (have) {
-        JT_FWD_COMPUTE_STEP
+        fwd_compute_step<C, REC, B16>(L, A, pm, j_, h_, lane, t);
         have = false;
       }
       __syncthreads();
     }
   } else {
     for (int tile = first + wv; tile < xs.hi; tile += stride) {
-      JT_FWD_GATHER_STEP
-      JT_FWD_COMPUTE_STEP
+      fwd_gather_step<C, REC, B16>(D, L, A, tile, j_, h_, lane, t);
+      fwd_compute_step<C, REC, B16>(L, A, pm, j_, h_, lane, t);
     }
   }
-#undef JT_FWD_GATHER_STEP
-#undef JT_FWD_COMPUTE_STEP
 }
 
 
@@ -445,9 +398,6 @@ __global__ __launch_bounds__(512, 2) void k_shade_bwd(Dev D, MlpDev M, PeMask pm
   const XcdShare xs = xcd_share(ntiles, nblk);  // tiles of neighbouring samples meet in one XCD's L2
   // (the two waves of a SIMD taking the chain and the scatter of their tiles in opposite order, in lock step by a workgroup
   //  barrier as in the inference forward, was measured here as well: 1.51 ms against 1.33 free-running, LLFF 0.68 / 0.65)
-#if JT_SETPRIO
-  if (wv >= B::NWAVE / 2) __builtin_amdgcn_s_setprio(1);
-#endif
   for (int tile = xs.lo + xs.rank * B::NWAVE + wv; tile < xs.hi; tile += xs.peers * B::NWAVE) {
     // re-materialise the lane indices per tile: otherwise every per-lane LDS address / select that depends
     // on them is hoisted out of the tile loop as a loop invariant and the kernel spills hundreds of VGPRs
@@ -1561,7 +1511,7 @@ static int env_int(const char* name, int dflt) {
 static Knobs read_env_knobs() {
   Knobs k;
   // which stages run on the bf16 matrix cores with three-piece operands (fp32-level accuracy, jt_shade_core.h): bit 0 the
-  // forward chain (k_shade_fwd_b16), bit 1 the weight-gradient GEMMs (k_wgrad<.., true>), bit 2 the chain of the SPLIT backward
+  // forward chain (k_shade_fwd<.., true>), bit 1 the weight-gradient GEMMs (k_wgrad<.., true>), bit 2 the chain of the SPLIT backward
   // (k_shade_bwd<..., SPLIT, B16>).  JT_BF16X3 overrides the build default; 0 = everything on the fp32 matrix cores.
   k.matrix_mode = env_int("JT_BF16X3", JT_BF16X3_DEFAULT) & 7;
   k.split = env_int("JT_BWD_SPLIT", -1);
@@ -1616,14 +1566,6 @@ struct KindTag { typedef C Cfg; };
 template <class F>
 static auto for_kind(int kind, F&& f) { return kind == 0 ? f(KindTag<CfgBlender>()) : f(KindTag<CfgLlff>()); }
 
-#if JT_STAMP
-extern "C" int jt_debug_read_stamps(unsigned long long* out8) {
-  if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_stamps), 8 * sizeof(unsigned long long)) != hipSuccess) return JT_ERR_ARG;
-  unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (hipMemcpyToSymbol(HIP_SYMBOL(g_stamps), z, sizeof(z)) != hipSuccess) return JT_ERR_ARG;
-  return JT_OK;
-}
-#endif
 #if JT_TILE_STAMP
 extern "C" int jt_debug_read_tile_stamps(unsigned long long* out16) {
   if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_tstamps), 16 * sizeof(unsigned long long)) != hipSuccess) return JT_ERR_ARG;
@@ -1794,21 +1736,23 @@ struct ShadeFwdArgs {
   float* rgb_s;
   hipStream_t st;
 };
+template <class C, int REC, bool B16>
+static void launch_shade_fwd_b(const ShadeFwdArgs& a, float* rec, int rows) {
+  typedef FwdShape<B16> S;
+  const long tiles = ((long)a.cap + 31) / 32;
+  const long blocks = std::min<long>((tiles + S::NW - 1) / S::NW, S::grid_cap());
+  const size_t lds = S::template lds_bytes<C>();
+  const auto kernel = k_shade_fwd<C, REC, B16>;
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(kernel, dim3((int)blocks), dim3(S::THREADS), lds, a.st, a.D, a.M, a.pm, a.rays_o, a.rays_d, a.jitter, a.zvals,
+                     a.tmin, a.offset, a.R, a.eray, a.esmp, a.vdir, a.rgb_s, rec, a.cap, rows);
+}
 template <class C, int REC>
 static int launch_shade_fwd_t(const ShadeFwdArgs& a, float* rec, const Knobs& k) {
-  const long tiles = ((long)a.cap + 31) / 32;
   const int rows = shade_tape<C>(k).rows;
-  auto launch = [&](auto kernel, long blocks, int threads, size_t lds) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kernel, dim3((int)blocks), dim3(threads), lds, a.st, a.D, a.M, a.pm, a.rays_o, a.rays_d, a.jitter, a.zvals,
-                       a.tmin, a.offset, a.R, a.eray, a.esmp, a.vdir, a.rgb_s, rec, a.cap, rows);
-  };
-  constexpr int NW = JT_B16_THREADS / 64;
-  // matrix-mode bit 0: the forward's matrix stages as six bf16 MFMAs per fp32 product sum (jt_shade_core.h), one 115 KB-LDS
-  // workgroup per CU
-  if (k.matrix_mode & 1)
-    launch(k_shade_fwd_b16<C, REC>, std::min<long>((tiles + NW - 1) / NW, chip().cus), JT_B16_THREADS, B16Cfg<C>::LDS_BYTES);
-  else launch(k_shade_fwd<C, REC>, std::min<long>((tiles + 3) / 4, 512), 256, C::LDS_FLOATS * sizeof(float));
+  // matrix-mode bit 0: the forward's matrix stages as six bf16 MFMAs per fp32 product sum (jt_shade_core.h)
+  if (k.matrix_mode & 1) launch_shade_fwd_b<C, REC, true>(a, rec, rows);
+  else launch_shade_fwd_b<C, REC, false>(a, rec, rows);
   JT_LAUNCH_CHECK();
   return JT_OK;
 }

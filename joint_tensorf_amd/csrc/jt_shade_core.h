@@ -359,6 +359,18 @@ __device__ inline void relu_(Hidden<C>& x) {
     for (int r = 0; r < 16; ++r) x.v[mt][r] = fmaxf(x.v[mt][r], 0.f);
 }
 
+// ReLU sign word of a lane's units of one hidden layer (x after relu_): bit mt * 16 + r <-> unit mt * 32 + rowmap(r, h).
+// The forward kernels store it, the backward kernels mask their gradients with it.
+template <class C>
+__device__ inline unsigned relu_signs(const Hidden<C>& x) {
+  unsigned mask = 0u;
+#pragma unroll
+  for (int mt = 0; mt < C::MT; ++mt)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) mask |= (x.v[mt][r] > 0.f) ? (1u << (mt * 16 + r)) : 0u;
+  return mask;
+}
+
 // view-direction encoding used by the WeakView last layer: [sin d (3x2) , cos d (3x2)] per channel
 __device__ inline void view_pe(const float vd[3], const PeMask& pm, float out[12]) {
 #pragma unroll

@@ -11,13 +11,15 @@ stores and float atomics.  4-byte-per-lane reads are outside the guide's calibra
 upper bound for them."""
 import csv
 import json
+import re
 import sys
 from collections import defaultdict
 
+# k_shade_fwd<config, REC, B16>: REC = 0 is the inference forward, 1..3 leave records (jt_shade.hip)
 KERNELS = {
-    "k_shade_bwd": "jt::k_shade_bwd<",
-    "k_shade_fwd_train": "true>(",
-    "k_shade_fwd_infer": "false>(",
+    "k_shade_bwd": r"jt::k_shade_bwd<",
+    "k_shade_fwd_train": r"jt::k_shade_fwd<.*>, [123], (?:true|false)>\(",
+    "k_shade_fwd_infer": r"jt::k_shade_fwd<.*>, 0, (?:true|false)>\(",
 }
 
 
@@ -26,7 +28,7 @@ def per_launch(path):
     for r in csv.DictReader(open(path)):
         nm = r["Kernel_Name"]
         for key, pat in KERNELS.items():
-            if pat in nm and ("k_shade_bwd" in nm or "k_shade_fwd" in nm):
+            if re.search(pat, nm):
                 a = acc[key]
                 a[0] += 1
                 a[1] += float(r["Counter_Value"])

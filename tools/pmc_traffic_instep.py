@@ -13,6 +13,7 @@ import json
 import sys
 from collections import defaultdict
 
+# ("jt::k_shade_fwd<": both matrix-core paths are instantiations of the one forward kernel; the profiled command runs no inference)
 KERNELS = {"k_shade_bwd": "jt::k_shade_bwd<", "k_shade_fwd_train": "jt::k_shade_fwd<",
            "k_march_bwd_walk": "jt::k_march_bwd_walk<", "k_march_bwd_scan": "jt::k_march_bwd_scan", "k_march_fwd": "jt::k_march_fwd"}
 
