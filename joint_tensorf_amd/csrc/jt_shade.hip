@@ -281,7 +281,9 @@ __device__ inline void scatter_plane(const Dev& D, const JtFactors& G, int pl, c
     aix = row16_sum(aix);
     aiy = row16_sum(aiy);
     ail = row16_sum(ail);
-    if (cl < 3) atomicAdd(&gxyz[sidx * 4 + my_axis], ((cl == 0) ? aix : (cl == 1) ? aiy : ail) * my_scale);
+    // (a plain read-add-write: the three lanes of a group hold three different axes, the planes follow one another behind
+    //  wave_lds_sync(), so a slot never has two writers in flight -- no LDS float atomic, see jt_lds_sum.h for its price)
+    if (cl < 3) gxyz[sidx * 4 + my_axis] += ((cl == 0) ? aix : (cl == 1) ? aiy : ail) * my_scale;
   };
   // the factor values are fetched two steps ahead of their use (three rotating buffers, steps fully unrolled)
   TapBuf<NCH> bufC;
@@ -714,6 +716,8 @@ __global__ __launch_bounds__(WAVES * 64) void k_shade_scatter(Dev D, MlpDev M, J
         geo[t * 4 + 0] = rec_ld(rt + (B::R_GEO + 0) * 32);
         geo[t * 4 + 1] = rec_ld(rt + (B::R_GEO + 1) * 32);
         geo[t * 4 + 2] = rec_ld(rt + (B::R_GEO + 2) * 32);
+        // (the walk stores all three axes of every slot before they are read, so this fill is redundant -- but without it the
+        //  twelve-wave VM-48 shape spills one more register, 12 -> 16 bytes of scratch; one LDS write per lane and batch stays)
         gxyz[t * 4 + 0] = gxyz[t * 4 + 1] = gxyz[t * 4 + 2] = 0.f;
       }
       // A operand of block b (steps 4 b .. 4 b + 3 of every group): row i = cl is step 4 b + (cl & 3) of group cl >> 2, the
@@ -754,7 +758,10 @@ __global__ __launch_bounds__(WAVES * 64) void k_shade_scatter(Dev D, MlpDev M, J
       wave_lds_sync();
       const float* P = D.aP[pl];
       const float* Ln = D.aL[pl];
-      RecWalker<NCH, C::CA, DET ? 1 : 0, LLINE> wk;
+      // (the 20-channel scatter keeps ds_add_f32 for its float line: its second channel group has 4 live lanes of 16, so a
+      //  flush of four groups pays the float atomic for 64 + 16 lanes, not 3 x 64, and the compare-and-swap sum measured 1.6 % SLOWER
+      //  there -- 346 against 341 us alone -- while VM-48 gains 3 % and the density walk 18 %; profiles/lds_line_sum.txt)
+      RecWalker<NCH, C::CA, DET ? 1 : 0, LLINE, (C::CA % 16 == 0) ? JT_LDS_LINE_SUM : 0> wk;
       wk.init(G.app_plane[pl], LLINE ? sline : G.app_line[pl], cl, DET, bad);
       const int m0 = kM0(pl), m1 = kM1(pl), mv = kV(pl);
       const int my_axis = (cl == 0) ? m0 : (cl == 1) ? m1 : mv;
@@ -780,7 +787,9 @@ __global__ __launch_bounds__(WAVES * 64) void k_shade_scatter(Dev D, MlpDev M, J
         aix = row16_sum(aix);
         aiy = row16_sum(aiy);
         ail = row16_sum(ail);
-        if (cl < 3) atomicAdd(gx0 + q * 4, ((cl == 0) ? aix : (cl == 1) ? aiy : ail) * my_scale);
+        // (a plain store: slot (group, step, axis) has this one writer, once per batch and plane, and is read behind
+        //  wave_lds_sync() -- as an LDS float atomic it cost 12 lanes x 3 cycles of the LDS unit per step)
+        if (cl < 3) gx0[q * 4] = ((cl == 0) ? aix : (cl == 1) ? aiy : ail) * my_scale;
       };
       TapBuf<NCH> bufA, bufB;
       float av[KS];

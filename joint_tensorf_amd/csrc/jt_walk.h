@@ -10,6 +10,7 @@
 // records, parity slots) is described below.
 #pragma once
 #include "jt_common.h"
+#include "jt_lds_sum.h"
 
 // an accumulator that never received anything needs no atomic
 #define JT_FLUSH_COND(x) ((x) != 0.f)
@@ -123,11 +124,13 @@ __device__ inline float row16_sum(float v) {
 // FX: 0 = float atomics, 1 = JT_DETERMINISTIC fixed point, 2 = chosen at run time by init()'s flag (a kernel that is
 // instantiated once; the density walk, short of registers, is instantiated per mode)
 // LDSL: the LINE gradients are added into a workgroup-private copy of the line in LDS (gL points there; LDS atomics, the owner
-// adds the copy into the real gradient once) instead of going out as global atomics.  1: a float copy (ds_add_f32);
+// adds the copy into the real gradient once) instead of going out as global atomics.  1: a float copy, summed by the lanes and
+// moved through the cell with an integer LDS atomic (jt_lds_sum.h; JT_LDS_LINE_SUM = 0: ds_add_f32 itself);
 // 2: a copy of DOUBLES, same element indexing (ds_add_f64) -- on gfx950 ds_add_f32 retires one lane every three cycles
 // (193 cycles per full wave instruction) while ds_add_f64 takes 9 (tools/lds_atomic_rate.hip), so the double copy is the one
 // to use wherever twice the bytes fit
-template <int NCH, int CA, int FX = 2, int LDSL = 0>
+// LSUM: the form that sums a float LDS line (jt_lds_sum.h; 0 = ds_add_f32), chosen per kernel by the caller
+template <int NCH, int CA, int FX = 2, int LDSL = 0, int LSUM = JT_LDS_LINE_SUM>
 struct RecWalker {
   float acc[4][NCH];   // plane accumulators, parity slots
   float accl[2][NCH];  // line accumulators, parity slots
@@ -197,7 +200,7 @@ struct RecWalker {
       for (int k = 0; k < NCH; ++k) {
         if (!live[k]) continue;
         if (LDSL == 2) atomicAdd(reinterpret_cast<double*>(reinterpret_cast<char*>(base) + 2u * (off + ck[k])), (double)a[k]);
-        else atomicAdd(reinterpret_cast<float*>(reinterpret_cast<char*>(base) + (off + ck[k])), a[k]);
+        else lds_sum<LSUM>(LdsCell{reinterpret_cast<float*>(reinterpret_cast<char*>(base) + (off + ck[k]))}, a[k]);
       }
     }
 #pragma unroll
