@@ -113,6 +113,14 @@ static int adam_launch(const JtAdamItem* items, int n_items, float beta1, float 
                        void* stream, const float* coefs_host = nullptr) {
   if (!items || n_items < 1) return JT_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
+  // every item is checked before the first launch: a call that fails has stepped nothing (with more than kAdamMaxItems items the
+  // launches in front of a bad item would otherwise have run)
+  for (int i = 0; i < n_items; ++i) {
+    const JtAdamItem& s = items[i];
+    if (!s.p || !s.g || !s.m || !s.v || s.n < 1) return JT_ERR_ARG;
+    if (!dyn && !coefs_host && (!(s.bias_correction1 > 0.f) || !(s.bias_correction2 > 0.f))) return JT_ERR_ARG;
+    if ((((uintptr_t)s.p | (uintptr_t)s.g | (uintptr_t)s.m | (uintptr_t)s.v) & 15) != 0) return JT_ERR_UNSUPPORTED;
+  }
   for (int first = 0; first < n_items; first += kAdamMaxItems) {
     AdamBatch B;
     B.dyn = dyn ? dyn + 2 * first : nullptr;
@@ -123,9 +131,6 @@ static int adam_launch(const JtAdamItem* items, int n_items, float beta1, float 
     int blocks = 0;
     for (int i = 0; i < B.n; ++i) {
       const JtAdamItem& s = items[first + i];
-      if (!s.p || !s.g || !s.m || !s.v || s.n < 1) return JT_ERR_ARG;
-      if (!dyn && !coefs_host && (!(s.bias_correction1 > 0.f) || !(s.bias_correction2 > 0.f))) return JT_ERR_ARG;
-      if ((((uintptr_t)s.p | (uintptr_t)s.g | (uintptr_t)s.m | (uintptr_t)s.v) & 15) != 0) return JT_ERR_UNSUPPORTED;
       AdamItemDev& d = B.t[i];
       d.p = s.p;
       d.g = s.g;

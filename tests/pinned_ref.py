@@ -220,6 +220,21 @@ class guard_band:
                 if bool((base[n:].view(torch.uint8) != GUARD_FILL).any())]
 
 
+class deterministic:
+    """with deterministic(on): the library's deterministic mode switched on (or off), restored on the way out"""
+
+    def __init__(self, on):
+        self.on = on
+
+    def __enter__(self):
+        from joint_tensorf_amd._lib import lib
+        self.lib, self.prev = lib, lib.jt_set_deterministic(1 if self.on else 0)
+
+    def __exit__(self, *exc):
+        self.lib.jt_set_deterministic(self.prev)
+        return False
+
+
 def _run_hip(tf, o, d, S, ndc, white, cot_seed, profile, pose_only):
     import contextlib
     from tests.fullsize_util import read_relu_masks

@@ -13,6 +13,7 @@ import torch
 
 from oracle import tensorf_oracle as O
 from tests.golden_util import Fixture
+from tests.pinned_ref import deterministic
 from tests.test_gpu_edge import _batch, _check_grads
 from tests.test_gpu_parity import build_scene
 
@@ -45,19 +46,6 @@ class spy_calls:
 
     def __exit__(self, *exc):
         self.ops.check = self.orig
-        return False
-
-
-class deterministic:
-    def __init__(self, on):
-        self.on = on
-
-    def __enter__(self):
-        from joint_tensorf_amd._lib import lib
-        self.lib, self.prev = lib, lib.jt_set_deterministic(1 if self.on else 0)
-
-    def __exit__(self, *exc):
-        self.lib.jt_set_deterministic(self.prev)
         return False
 
 
