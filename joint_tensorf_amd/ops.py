@@ -589,6 +589,15 @@ def _shade_forward(scene, fac, mlp, t, rgb_s, ws, nbytes, st):
                                *ws_args, st), "jt_shade_forward")
 
 
+def _reg_args(sdp, sdl, sap, tv_density, tv_app):
+    """(hw[9], Cd, Ca, TV on the density, TV on the colours) of factor storages, as jt_reg_losses_* take them"""
+    hw = []
+    for i in range(3):
+        H, W, _ = sdp[i].shape
+        hw += [H, W, sdl[i].shape[0]]
+    return (ctypes.c_int32 * 9)(*hw), sdp[0].shape[2], sap[0].shape[2], int(bool(tv_density)), int(bool(tv_app))
+
+
 def _reg_backward(reg, fac, g_reg, gfac, accumulate, dev, st):
     """jt_reg_losses_backward: the regularisers' gradient under dL/d reg3 = g_reg (None: zeros) written over (accumulate 0) or
     added into (1) the factor gradients"""
@@ -701,11 +710,7 @@ class RenderRays(torch.autograd.Function):
         # add kernel that allocates a third tensor (6 adds and 31 MB x 3 of traffic per iteration at 400^3)
         reg3 = reg = pre = None
         if plan.reg is not None:
-            hw = []
-            for i in range(3):
-                H, W, _ = sdp[i].shape
-                hw += [H, W, sdl[i].shape[0]]
-            reg = ((ctypes.c_int32 * 9)(*hw), sdp[0].shape[2], sap[0].shape[2], int(bool(flags[0])), int(bool(flags[1])))
+            reg = _reg_args(sdp, sdl, sap, flags[0], flags[1])
             scratch = _reg_scratch(dev)
             reg3 = torch.empty(3, **f32)
             if plan.reg == "fused":
@@ -1089,35 +1094,23 @@ class RegLosses(torch.autograd.Function):
         dp, dl, ap, al = factors[0:3], factors[3:6], factors[6:9], factors[9:12]
         st_ = [[factor_storage(p) for p in lst] for lst in (dp, dl, ap, al)]
         dev = st_[0][0].device
-        hw = []
-        for i in range(3):
-            H, W, _ = st_[0][i].shape
-            hw += [H, W, st_[1][i].shape[0]]
-        hw_arr = (ctypes.c_int32 * 9)(*hw)
-        fac = _factors_struct(*st_)
-        scratch = _reg_scratch(dev)
+        reg = _reg_args(st_[0], st_[1], st_[2], with_tv_density, with_tv_app)
         out = torch.empty(3, device=dev, dtype=torch.float32)
-        Cd, Ca = st_[0][0].shape[2], st_[2][0].shape[2]
-        check(lib.jt_reg_losses_forward(fac, hw_arr, Cd, Ca, int(bool(with_tv_density)), int(bool(with_tv_app)),
-                                        ptr(scratch), ptr(out), _stream()), "jt_reg_losses_forward")
-        ctx.saved = (st_, hw, Cd, Ca, bool(with_tv_density), bool(with_tv_app))
+        check(lib.jt_reg_losses_forward(_factors_struct(*st_), *reg, ptr(_reg_scratch(dev)), ptr(out), _stream()),
+              "jt_reg_losses_forward")
+        ctx.saved = (st_, reg)
         return out
 
     @staticmethod
     def backward(ctx, g3):
-        st_, hw, Cd, Ca, wd, wa = ctx.saved
-        dev = st_[0][0].device
-        hw_arr = (ctypes.c_int32 * 9)(*hw)
-        fac = _factors_struct(*st_)
+        st_, reg = ctx.saved
+        wa = reg[4]
         # every element is written (accumulate = 0): no zero fill of the 31 MB / 123 MB buffers
         gd = [torch.empty_like(t) for t in st_[0]]
         gl = [torch.empty_like(t) for t in st_[1]]
         ga = [torch.empty_like(t) for t in st_[2]] if wa else [None] * 3
         gfac = _factors_struct(gd, gl, ga if wa else st_[2], st_[3])  # unused slots just need a non-null pointer
-        scratch = torch.empty(36, device=dev, dtype=torch.float32)
-        g3c = g3.contiguous().float()
-        check(lib.jt_reg_losses_backward(fac, hw_arr, Cd, Ca, ptr(g3c), int(wd), int(wa), gfac, 0, ptr(scratch),
-                                         _stream()), "jt_reg_losses_backward")
+        _reg_backward(reg, _factors_struct(*st_), g3, gfac, 0, st_[0][0].device, _stream())
         grads = [factor_logical(t) for t in gd] + [factor_logical(t) for t in gl] + \
                 [factor_logical(t) if t is not None else None for t in ga] + [None] * 3
         return (None, None) + tuple(grads)

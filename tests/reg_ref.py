@@ -6,7 +6,7 @@ Everything is written with slices and no autograd: a 25 M-element tensor costs a
 
 The gradient of  c0 sum|x| + c1 sum (x[y+1] - x[y])^2 + c2 sum (x[., x+1] - x[., x])^2  at an element is
     c0 sign(x) + 2 c1 A + 2 c2 B,   A = [y > 0] (x - up) - [y + 1 < H] (down - x),   B likewise along W,
-with sign(0) = 0 (torch's abs backward, and the kernels' (v > 0) - (v < 0))."""
+with sign(0) = 0 (torch's abs backward, and reg_texel's (v > 0) - (v < 0))."""
 import functools
 
 import torch
@@ -24,10 +24,10 @@ CAPS = {"factor_fwd": (1024, None), "factor_bwd": (2048, 2048), "batch_fwd": (51
 
 def launch_shape(entry, H, W, C, tv, deterministic=False):
     """(form, workgroups, items, max_trips) of one tensor in `entry`'s launch.  tv: the kernel's TV switch -- the template
-    argument of the forward and fused bodies, "a TV coefficient is non-zero" in the backward.  form "walk": a thread takes
-    (segment of REG_SEG rows, column, quad) items, "general": one quad per item.  max_trips: the most iterations any thread's
-    grid-stride loop makes.  Deterministic mode changes the batched forward alone (one workgroup per tensor); the fused entry
-    point refuses it."""
+    argument of reg_body -- the item's flag in the forward and fused kernels, "a TV coefficient is non-zero" in the
+    backward.  form "walk": a thread takes (segment of REG_SEG rows, column, quad) items, "general": one quad per item.
+    max_trips: the most iterations any thread's grid-stride loop makes.  Deterministic mode changes the batched forward alone
+    (one workgroup per tensor); the fused entry point refuses it."""
     assert C % 4 == 0 and H >= 1 and W >= 1
     cap = CAPS[entry][0 if tv else 1]
     if cap is None:

@@ -1,10 +1,11 @@
-"""The regulariser kernels (csrc/jt_reg.hip) on both loop forms of all three bodies, held to the float64 closed forms of
-tests/reg_ref.py element by element, with bounds that are derived, not measured.
+"""The five regulariser kernels (csrc/jt_reg.hip) -- every instantiation of the one loop pair reg_body<TV, OUT>, on the row walk
+and on the general loop -- held to the float64 closed forms of tests/reg_ref.py element by element, with bounds that are
+derived, not measured.
 
 Launch arithmetic (mirrored by reg_ref.launch_shape, whose constants tests/test_reg_ref.py reads out of the source).  A tensor
 [H][W][C] has H W C/4 quads and gets min(ceil(quads / 256), cap) workgroups of 256 threads; cap (TV | no TV) is 1 024 for the
 per-tensor forward, 2 048 | 2 048 for both backwards, 512 | 128 for the batched forward, 1 024 | 256 for the fused launch.
-With TV and H >= 32 the bodies WALK: an item is (segment of 16 rows, column, quad), ceil(H / 16) W C/4 of them, and a thread
+With TV and H >= 32 the loop pair WALKS: an item is (segment of 16 rows, column, quad), ceil(H / 16) W C/4 of them, and a thread
 carries the vertical neighbours through registers from row to row; otherwise the GENERAL loop takes one quad per item.  The
 backward walks when a TV coefficient is non-zero.  Both loops are grid-stride: a thread makes ceil(items / (256 workgroups))
 trips at most.  In deterministic mode the batched forward runs ONE workgroup per tensor and the fused entry point refuses.
@@ -32,7 +33,6 @@ Every gradient and output buffer has a tail of NaN-patterned words behind it tha
 write in full starts out with that pattern too, so an element nobody wrote fails.  After every batched call the persistent
 scratch (ops._reg_scratch) is all zero."""
 import ctypes
-import os
 
 import pytest
 import torch
@@ -155,7 +155,6 @@ def _shape_is(entry, key, tv, form, trips, deterministic=False):
 def _api():
     from joint_tensorf_amd import ops
     from joint_tensorf_amd._lib import lib, ptr
-    assert "JT_REG_BLOCKS" not in os.environ and "JT_REG_FUSED_BLOCKS" not in os.environ    # (they replace the caps)
     return ops, lib, ptr
 
 

@@ -91,21 +91,31 @@ def test_mirror_constants_are_the_sources():
     src = _source("jt_reg.hip")
     assert int(re.search(r"constexpr int kRegSeg = (\d+);", src).group(1)) == R.REG_SEG
     assert int(re.search(r"constexpr int kRegShards = (\d+);", src).group(1)) == R.REG_SHARDS
-    assert len(re.findall(r"H >= 2 \* kRegSeg\)", src)) == 3          # the three bodies' walk condition
-    assert len(re.findall(r"dim3\((?:blocks|nblk)\), dim3\((\d+)\)", src)) == 5 and \
-        set(re.findall(r"dim3\((?:blocks|nblk)\), dim3\((\d+)\)", src)) == {str(R.THREADS)}
-    cap1 = r"min\(\(total \+ 255\) / 256, (\d+)L\)"
-    cap2 = r"min\(\(total \+ 255\) / 256, max_blocks > 0 \? max_blocks : \(tv \? (\d+)L : (\d+)L\)\)"
-    found = {
-        "factor_fwd": (int(re.search(cap1, _entry(src, "jt_factor_reg_forward")).group(1)), None),
-        "factor_bwd": (int(re.search(cap1, _entry(src, "jt_factor_reg_backward")).group(1)),) * 2,
-        "batch_fwd": tuple(int(v) for v in re.search(cap2, _entry(src, "jt_reg_losses_forward")).groups()),
-        "batch_bwd": (int(re.search(cap1, _entry(src, "jt_reg_losses_backward")).group(1)),) * 2,
-        "fused": tuple(int(v) for v in re.search(cap2, _entry(src, "jt_reg_losses_fused")).groups()),
-    }
-    assert found == R.CAPS
-    assert "if (jt_deterministic()) blocks = 1;" in _entry(src, "jt_reg_losses_forward")
-    assert "if (jt_deterministic()) return JT_ERR_UNSUPPORTED;" in _entry(src, "jt_reg_losses_fused")
+    assert len(re.findall(r"H >= 2 \* kRegSeg", src)) == 1            # the one loop pair's walk condition
+    # the five launches, one per entry point, all of 256 threads; the quad-to-workgroup helper divides by the same number
+    launches = re.findall(r"hipLaunchKernelGGL\((\w+)(?:<true>)?, dim3\((?:blocks|nblk)\), dim3\((\d+)\)", src)
+    assert len(launches) == src.count("hipLaunchKernelGGL(") == 5 and {t for _, t in launches} == {str(R.THREADS)}
+    assert sorted(k for k, _ in launches) == ["k_factor_reg_bwd", "k_factor_reg_fwd", "k_reg_batch_bwd", "k_reg_batch_fused",
+                                              "k_reg_batch_fwd"]
+    helper = src[src.index("static int reg_blocks("):src.index('extern "C" int jt_factor_reg_forward(')]
+    assert "(quads + %d) / %d, kRegCaps[entry][tv ? 0 : 1]" % (R.THREADS - 1, R.THREADS) in helper
+    assert src.count("+ 255) / 256") == 1 and "getenv" not in src      # no second cap arithmetic, no override
+    # the caps table: one row per entry point, in the enum's order; a cap of 0 stands for "never launched that way"
+    rows = re.findall(r"/\* (kReg\w+) \*/ \{(\d+), (\d+)\}", src[src.index("kRegCaps[][2] = {"):src.index("static int reg_blocks(")])
+    assert [r[0] for r in rows] == re.search(r"enum RegEntry \{ ([\w, ]+) \};", src).group(1).split(", ")
+    caps = {name: (int(tv), int(no) or None) for name, tv, no in rows}
+    # the row each entry point asks for its workgroups under
+    asks = {"factor_fwd": "jt_factor_reg_forward", "factor_bwd": "jt_factor_reg_backward", "batch_fwd": "jt_reg_losses_forward",
+            "batch_bwd": "jt_reg_losses_backward", "fused": "jt_reg_losses_fused"}
+    row = {e: re.findall(r"reg_(?:blocks|batch)\((kReg\w+), ", _entry(src, fn)) for e, fn in asks.items()}
+    assert all(len(r) == 1 for r in row.values()) and len({r[0] for r in row.values()}) == 5
+    assert {e: caps[r[0]] for e, r in row.items()} == R.CAPS
+    builder = src[src.index("static int reg_batch("):src.index('extern "C" int jt_reg_losses_forward(')]
+    assert "int blocks = reg_blocks(entry, tv, t.H, t.W, t.C);" in builder
+    assert "if (entry == kRegBatchFwd && jt_deterministic()) blocks = 1;" in builder
+    assert "jt_deterministic()" not in _entry(src, "jt_reg_losses_forward") + _entry(src, "jt_reg_losses_backward")
+    fused = _entry(src, "jt_reg_losses_fused")
+    assert fused.index("if (jt_deterministic()) return JT_ERR_UNSUPPORTED;") < fused.index("reg_batch(")   # before any write
     opt = _source("jt_optim.hip")
     assert int(re.search(r"constexpr int kAdamMaxItems = (\d+);", opt).group(1)) == A.MAX_ITEMS
     assert re.search(r"constexpr int kAdamElemsPerBlock = 256 \* 4 \* 4;", opt) and A.ELEMS_PER_BLOCK == 4096
