@@ -412,7 +412,9 @@ int jt_factor_reg_backward(const float* x, int H, int W, int C, const float* coe
  * gather: rgb [B][r][3], image [B][3][n_pixels], ray_idx [r] int64; edge_mask [B][n_pixels] u8 or NULL.
  *   edge_mask == NULL: loss = nanmean((rgb - img)^2)
  *   else             : loss = edge_factor * nanmean((rgb*m - img*m)^2) + non_edge_factor * nanmean((rgb*(1-m) - img*(1-m))^2)
- * acc4: 4 floats of device scratch shared by forward and backward; g_loss: dL/dloss on the device. */
+ * acc4: 4 floats of device scratch shared by forward and backward; g_loss: dL/dloss on the device.
+ * The kernels index colours with 32 bits: 3 * n_views * rays_per_view >= 2^31 is JT_ERR_UNSUPPORTED, forward and backward, direct
+ * and _ind. */
 int jt_render_loss_forward(const float* rgb, const float* image, const int64_t* ray_idx, const uint8_t* edge_mask,
                            int n_views, int rays_per_view, int n_pixels, float edge_factor, float non_edge_factor,
                            float* acc4, float* loss, void* stream);
@@ -421,7 +423,9 @@ int jt_render_loss_backward(const float* rgb, const float* image, const int64_t*
                             const float* acc4, const float* g_loss, float* g_rgb, void* stream);
 /* One photometric nanmean PER VIEW over a ragged batch (layout as jt_raygen_forward_ragged; image [n_views][3][n_pixels], no edge
  * mask): loss [n_views], acc2 [n_views][2] = (sum of squares, count) kept for the backward, g_rgb[i] = g_loss[view of i] * 2 (rgb -
- * gt) / count -- the single-view jt_render_loss_forward / backward bit for bit. */
+ * gt) / count -- the single-view jt_render_loss_forward / backward bit for bit.  The same 32-bit limit: the backward returns
+ * JT_ERR_UNSUPPORTED for 3 * n_rays >= 2^31; the forward cannot see the counts (view_offset is device memory), so a caller
+ * that has not been through the backward's check must keep every view below 2^31 / 3 rays itself. */
 int jt_render_loss_views_forward(const float* rgb, const float* image, const int64_t* ray_idx, const int32_t* view_offset,
                                  int n_views, int n_pixels, float* acc2, float* loss, void* stream);
 int jt_render_loss_views_backward(const float* rgb, const float* image, const int64_t* ray_idx, const int32_t* view_offset,

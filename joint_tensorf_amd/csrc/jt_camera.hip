@@ -221,16 +221,6 @@ __device__ inline PixRay pixel_ray(const float* P, const float* Ki, long idx, in
   return r;
 }
 
-// view of ray t in a RAGGED batch (view b owns rays view_offset[b] .. view_offset[b + 1] - 1): the last b with offset <= t
-__device__ inline int ragged_view(const int* __restrict__ voff, int V, int t) {
-  int lo = 0, hi = V - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (voff[mid] <= t) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
 // RAGGED = false: B views x the SAME r pixels (ray_idx [r]).  RAGGED = true: every view its own pixel list, concatenated
 // (ray_idx [n_total], view_offset [B + 1]; `r` is n_total) -- per ray the same arithmetic, so a view's rays are bit-identical
 // whether it is rendered alone or in a batch of views (batched test-time pose optimisation).

@@ -314,6 +314,16 @@ __device__ inline float wave_sum(float v) {
   return v;
 }
 
+// view of ray t in a RAGGED batch (view b owns rays view_offset[b] .. view_offset[b + 1] - 1): the last b with offset <= t
+__device__ inline int ragged_view(const int* __restrict__ voff, int V, int t) {
+  int lo = 0, hi = V - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (voff[mid] <= t) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
 __device__ inline void load_ray(const Dev& D, const float* rays_o, const float* rays_d, const float* jitter,
                                 const float* tmin_in, int ray, Ray& r) {
 #pragma unroll

@@ -89,16 +89,21 @@ def status_word(dev):
     return _STATUS[key]
 
 
-def finite_check(tensors_and_bits):
-    """one launch: OR `bit` into the device's status word for every (tensor, bit) that holds a non-finite value"""
-    items = [(t.detach(), b) for t, b in tensors_and_bits if t is not None and t.numel() > 0]
-    if not items:
-        return
+def _finite_items(check_items):
+    """(JtFiniteItem array, count, the fp32 contiguous tensors it points into) of [(tensor, status bit)]"""
+    items = [(t.detach(), b) for t, b in (check_items or ()) if t is not None and t.numel() > 0]
     keep = [t if (t.is_contiguous() and t.dtype == torch.float32) else t.contiguous().float() for t, _ in items]
-    arr = (_lib.JtFiniteItem * len(items))()
+    arr = (_lib.JtFiniteItem * max(len(items), 1))()
     for k, (t, (_, b)) in enumerate(zip(keep, items)):
         arr[k].data, arr[k].n, arr[k].bit = ptr(t), t.numel(), int(b)
-    check(lib.jt_finite_check(arr, len(items), ptr(status_word(keep[0].device)), _stream()), "jt_finite_check")
+    return arr, len(items), keep
+
+
+def finite_check(tensors_and_bits):
+    """one launch: OR `bit` into the device's status word for every (tensor, bit) that holds a non-finite value"""
+    arr, n, keep = _finite_items(tensors_and_bits)
+    if n:
+        check(lib.jt_finite_check(arr, n, ptr(status_word(keep[0].device)), _stream()), "jt_finite_check")
 
 
 def read_status(dev, clear=True):
@@ -1130,13 +1135,23 @@ def register_unit_seed(t):
     return t
 
 
-def _finite_items(check_items):
-    items = [(t.detach(), b) for t, b in (check_items or ()) if t is not None and t.numel() > 0]
-    keep = [t if (t.is_contiguous() and t.dtype == torch.float32) else t.contiguous().float() for t, _ in items]
-    arr = (_lib.JtFiniteItem * max(len(items), 1))()
-    for k, (t, (_, b)) in enumerate(zip(keep, items)):
-        arr[k].data, arr[k].n, arr[k].bit = ptr(t), t.numel(), int(b)
-    return arr, len(items), keep
+def _loss_sum_forward(ctx, render, reg3, w_host, w4_dev, check_items, loss_bit):
+    """the forward of LossSum (w_host: four floats) and LossSumDyn (w4_dev: device tensor [4]): one launch, with the guard when
+    check_items is given"""
+    r = render.detach().reshape(1).float()
+    q = reg3.detach().contiguous().float()
+    out = torch.empty(1, device=r.device, dtype=torch.float32)
+    if check_items is not None:
+        arr, n, keep = _finite_items(check_items)
+        w = (ctypes.c_float * 4)(*w_host) if w_host is not None else None
+        check(lib.jt_loss_sum_check_forward(ptr(r), ptr(q), w, ptr(w4_dev), ptr(out), arr, n, int(loss_bit),
+                                            ptr(status_word(r.device)), _stream()), "jt_loss_sum_check_forward")
+    elif w_host is not None:
+        check(lib.jt_loss_sum_forward(ptr(r), ptr(q), *w_host, ptr(out), _stream()), "jt_loss_sum_forward")
+    else:
+        check(lib.jt_loss_sum_forward_dyn(ptr(r), ptr(q), ptr(w4_dev), ptr(out), _stream()), "jt_loss_sum_forward_dyn")
+    ctx.render_shape = render.shape
+    return out[0]
 
 
 class LossSum(torch.autograd.Function):
@@ -1149,20 +1164,8 @@ class LossSum(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, render, reg3, w_render, w_l1, w_tvd, w_tvc, check_items=None, loss_bit=0):
-        r = render.detach().reshape(1).float()
-        q = reg3.detach().contiguous().float()
-        out = torch.empty(1, device=r.device, dtype=torch.float32)
-        if check_items is not None:
-            arr, n, keep = _finite_items(check_items)
-            w = (ctypes.c_float * 4)(w_render, w_l1, w_tvd, w_tvc)
-            check(lib.jt_loss_sum_check_forward(ptr(r), ptr(q), w, None, ptr(out), arr, n, int(loss_bit),
-                                                ptr(status_word(r.device)), _stream()), "jt_loss_sum_check_forward")
-        else:
-            check(lib.jt_loss_sum_forward(ptr(r), ptr(q), w_render, w_l1, w_tvd, w_tvc, ptr(out), _stream()),
-                  "jt_loss_sum_forward")
         ctx.w = (float(w_render), float(w_l1), float(w_tvd), float(w_tvc))
-        ctx.render_shape = render.shape
-        return out[0]
+        return _loss_sum_forward(ctx, render, reg3, ctx.w, None, check_items, loss_bit)
 
     @staticmethod
     def backward(ctx, g):
@@ -1253,18 +1256,8 @@ class LossSumDyn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, render, reg3, w4, check_items=None, loss_bit=0):
-        r = render.detach().reshape(1).float()
-        q = reg3.detach().contiguous().float()
-        out = torch.empty(1, device=r.device, dtype=torch.float32)
-        if check_items is not None:
-            arr, n, keep = _finite_items(check_items)
-            check(lib.jt_loss_sum_check_forward(ptr(r), ptr(q), None, ptr(w4), ptr(out), arr, n, int(loss_bit),
-                                                ptr(status_word(r.device)), _stream()), "jt_loss_sum_check_forward")
-        else:
-            check(lib.jt_loss_sum_forward_dyn(ptr(r), ptr(q), ptr(w4), ptr(out), _stream()), "jt_loss_sum_forward_dyn")
         ctx.w4 = w4
-        ctx.render_shape = render.shape
-        return out[0]
+        return _loss_sum_forward(ctx, render, reg3, None, w4, check_items, loss_bit)
 
     @staticmethod
     def backward(ctx, g):
@@ -1303,40 +1296,36 @@ class RenderLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, rgb, image, ray_idx, edge_mask, edge_factor, non_edge_factor):
         rgb_c = rgb.detach().contiguous().float()
-        B, r = rgb_c.shape[0], rgb_c.shape[1]
-        img = image.detach().contiguous().float().view(B, 3, -1)
+        img = image.detach().contiguous().float().view(rgb_c.shape[0], 3, -1)
         idx = ray_idx.detach().contiguous().to(torch.int64)
         m = None if edge_mask is None else edge_mask.detach().contiguous().to(torch.uint8)
-        dev = rgb_c.device
-        acc = torch.empty(4, device=dev, dtype=torch.float32)
-        loss = torch.empty(1, device=dev, dtype=torch.float32)
+        acc = torch.empty(4, device=rgb_c.device, dtype=torch.float32)
+        loss = torch.empty(1, device=rgb_c.device, dtype=torch.float32)
         slots = SUPERVISION_SLOTS_STATIC
         if slots is not None:
             # the caller's slots name buffers of exactly this layout (it pokes img / m -like tensors' addresses)
             assert img.data_ptr() == image.data_ptr() and (m is None or m.data_ptr() == edge_mask.data_ptr())
-            check(lib.jt_render_loss_forward_ind(ptr(rgb_c), ptr(slots), ptr(idx), int(m is not None), B, r, img.shape[2],
-                                                 float(edge_factor), float(non_edge_factor), ptr(acc), ptr(loss),
-                                                 _stream()), "jt_render_loss_forward_ind")
-        else:
-            check(lib.jt_render_loss_forward(ptr(rgb_c), ptr(img), ptr(idx), ptr(m), B, r, img.shape[2],
-                                             float(edge_factor), float(non_edge_factor), ptr(acc), ptr(loss), _stream()),
-                  "jt_render_loss_forward")
         ctx.saved = (rgb_c, img, idx, m, acc, float(edge_factor), float(non_edge_factor), slots)
+        RenderLoss._call("forward", ctx.saved, ptr(acc), ptr(loss))
         return loss[0]
 
     @staticmethod
+    def _call(way, saved, *tail):
+        """jt_render_loss_<way>, or its _ind form when the supervising buffers are named by `slots`"""
+        rgb_c, img, idx, m, _, fe, fne, slots = saved
+        if slots is not None:
+            name, target = "jt_render_loss_%s_ind" % way, (ptr(slots), ptr(idx), int(m is not None))
+        else:
+            name, target = "jt_render_loss_%s" % way, (ptr(img), ptr(idx), ptr(m))
+        check(getattr(lib, name)(ptr(rgb_c), *target, rgb_c.shape[0], rgb_c.shape[1], img.shape[2], fe, fne, *tail, _stream()),
+              name)
+
+    @staticmethod
     def backward(ctx, g):
-        rgb_c, img, idx, m, acc, fe, fne, slots = ctx.saved
-        B, r = rgb_c.shape[0], rgb_c.shape[1]
+        rgb_c, acc = ctx.saved[0], ctx.saved[4]
         gc = g.contiguous().float().view(1)
         g_rgb = torch.empty_like(rgb_c)
-        if slots is not None:
-            check(lib.jt_render_loss_backward_ind(ptr(rgb_c), ptr(slots), ptr(idx), int(m is not None), B, r,
-                                                  img.shape[2], fe, fne, ptr(acc), ptr(gc), ptr(g_rgb), _stream()),
-                  "jt_render_loss_backward_ind")
-        else:
-            check(lib.jt_render_loss_backward(ptr(rgb_c), ptr(img), ptr(idx), ptr(m), B, r, img.shape[2], fe, fne,
-                                              ptr(acc), ptr(gc), ptr(g_rgb), _stream()), "jt_render_loss_backward")
+        RenderLoss._call("backward", ctx.saved, ptr(acc), ptr(gc), ptr(g_rgb))
         return g_rgb, None, None, None, None, None
 
 

@@ -124,6 +124,26 @@ def test_bad_arguments_are_rejected_without_a_gpu():
     assert _lib.lib.jt_finite_check(None, 0, None, None) == 1
 
 
+def test_render_loss_refuses_2_pow_31_colours_without_a_gpu():
+    """The loss-head kernels index colours with 32 bits: every render-loss entry point that can see the count returns
+    JT_ERR_UNSUPPORTED (2) at 3 n_views rays_per_view >= 2^31 before it launches anything -- forward and backward, direct and
+    _ind, and the per-view backward at 3 n_rays >= 2^31.  Nothing here reaches a launch."""
+    from joint_tensorf_amd import _lib
+    L, p = _lib.lib, 64                     # p: a non-NULL pointer that is never dereferenced on these paths
+    B, r = 1 << 15, 1 << 15                 # 3 B r = 3 x 2^30
+    assert 3 * B * r >= 1 << 31
+    assert L.jt_render_loss_forward(p, p, p, None, B, r, 1, 1.0, 1.0, p, p, None) == 2
+    assert L.jt_render_loss_backward(p, p, p, None, B, r, 1, 1.0, 1.0, p, p, p, None) == 2
+    assert L.jt_render_loss_forward_ind(p, p, p, 1, B, r, 1, 1.0, 1.0, p, p, None) == 2
+    assert L.jt_render_loss_backward_ind(p, p, p, 1, B, r, 1, 1.0, 1.0, p, p, p, None) == 2
+    n_rays = 715827883                      # ceil(2^31 / 3)
+    assert 3 * n_rays >= 1 << 31 > 3 * (n_rays - 1)
+    assert L.jt_render_loss_views_backward(p, p, p, p, 1, n_rays, 1, p, p, p, None) == 2
+    # argument errors still come first
+    assert L.jt_render_loss_forward(None, p, p, None, B, r, 1, 1.0, 1.0, p, p, None) == 1
+    assert L.jt_render_loss_views_backward(None, p, p, p, 1, n_rays, 1, p, p, p, None) == 1
+
+
 if __name__ == "__main__":
     import sys
     if "--update" in sys.argv:

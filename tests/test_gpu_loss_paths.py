@@ -1,17 +1,27 @@
 """The loss-head kernels (jt_loss.hip) on every launch path, held to the float64 oracle with bounds that are derived, not
 measured: the photometric loss and its gradient, its per-view form, the weighted sum and the finiteness guard.
 
-Launch arithmetic the rows rest on (n = 3 B r colours):
-  n <= 32 768   k_render_loss_fwd_one: ONE workgroup of 1 024 threads; thread t takes t, t + 1 024, ... fetched eight at a
-                time, so a trip of the outer loop covers 8 192 elements: n = 3 (one live thread), 1 023 | 1 026 (the
-                second element of thread 0 and 1), 8 190 | 8 193 (a second eight-deep trip for thread 0 alone: seven of its
-                eight fetches are clamped to n - 1 and must not be summed), 32 766 (four trips, the last single-workgroup n).
-  n > 32 768    k_loss_zero, k_render_loss_fwd (min(ceil(n / 256), 512) workgroups of 256, atomic adds of the four sums),
-                k_render_loss_final: n = 32 769 is 129 workgroups; the grid is full at 512 x 256 = 131 072 threads and
+Launch arithmetic the rows rest on (n = 3 B r colours).  The three forward kernels share ONE walk (walk_sums<U> in
+jt_loss.hip): a thread takes first, first + stride, ... in that order, fetched U at a time with 32-bit indices, so a trip of
+the walk covers U x stride colours; a fetch past n is clamped to n - 1 and must not be summed.  U = 8 where one workgroup
+walks a whole batch (k_render_loss_fwd_one, k_render_loss_fwd<8> in deterministic mode), U = 1 where a thread owns a few
+colours (k_render_loss_fwd<1> under the full grid, the per-view kernel); the sums do not depend on U.
+  n <= 32 768   k_render_loss_fwd_one: ONE workgroup of 1 024 threads, first = thread, stride = 1 024, a trip covers 8 192
+                colours: n = 3 (one live thread), 1 023 | 1 026 (the second element of thread 0 and 1), 8 190 | 8 193 (a
+                second eight-deep trip for thread 0 alone: seven of its eight fetches are clamped), 32 766 (four trips, the
+                last single-workgroup n).
+  n > 32 768    k_loss_zero, k_render_loss_fwd<1> (min(ceil(n / 256), 512) workgroups of 256, first = global thread, stride
+                = the grid, one colour per trip, atomic adds of the four sums), k_render_loss_final: n = 32 769 is 129
+                workgroups and every live thread makes one trip; the grid is full at 512 x 256 = 131 072 threads, where
                 n = 131 076 sends four threads on a grid-stride second trip -- in k_render_loss_bwd as well, which has the
-                same grid at every n.  In deterministic mode the same kernel runs as ONE workgroup (129 / 513 trips).
-  per view      k_render_loss_views_fwd: one 1 024-thread workgroup per view with k_render_loss_fwd_one's summation order;
-                k_render_loss_views_bwd finds a colour's view by bisection over the offsets.
+                same grid at every n.  In deterministic mode k_render_loss_fwd<8> runs as ONE workgroup: stride = 256, an
+                eight-deep trip covers 2 048 colours, 17 trips at n = 32 769 (thread 0 sums 129 elements, one in its
+                last trip, whose other seven fetches are clamped) and 65 at n = 131 076.
+  per view      k_render_loss_views_fwd: one 1 024-thread workgroup per view running k_render_loss_fwd_one's body, one
+                colour per trip, on that view's colours (a view of 10 923 rays: 33 trips, the last for thread 0 alone; an
+                empty view: none);
+                k_render_loss_views_bwd finds a colour's view by bisection over the offsets (ragged_view) and forms the
+                gradient with k_render_loss_bwd's function.
   guard         k_finite_check: min(ceil(max n / 256), 256) workgroups of 256: 65 536 elements fill the grid, 65 537 sends
                 thread 0 on a second trip.
 
