@@ -39,9 +39,9 @@ extern "C" {
  * jt_shade_lean_tape / jt_shade_set_lean_tape, the workspace no longer carries the tile lists unless that variant is selected;
  * 1201: + jt_chip_geometry; 1202: + jt_shade_workspace_layout; 1203: + jt_march_forward_pose / jt_march_backward_pose; 1204: +
  * jt_lattice_indices; 1205: + jt_ssim_forward / jt_ssim_workspace_bytes; 1206: +
- * jt_image_ingest / jt_image_ingest_workspace_bytes; 1207: + jt_shade_backward_plan / jt_march_backward_plan.  Additions bump the last two digits, anything a caller built against the old header would get wrong bumps the
+ * jt_image_ingest / jt_image_ingest_workspace_bytes; 1207: + jt_shade_backward_plan / jt_march_backward_plan; 1208: + jt_mesh_count / jt_mesh_emit.  Additions bump the last two digits, anything a caller built against the old header would get wrong bumps the
  * hundreds). */
-#define JT_VERSION 1207
+#define JT_VERSION 1208
 
 #define JT_OK 0
 #define JT_ERR_ARG 1         /* null pointer / bad size */
@@ -573,6 +573,32 @@ int jt_adam_step_coefs(const JtAdamItem* items, int n_items, float beta1, float 
  * The per-iteration host scalars of the reference's loop -- lattice offsets (model/nerf.py:663), Adam coefficients
  * (model/tensorf.py:441-447 decays the lr every iteration) -- reach a replayed hipGraph this way. */
 int jt_poke(void* dst, const uint32_t* words, int n_words, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Iso-surface of a scalar lattice as a triangle mesh (csrc/jt_mesh.hip): marching tetrahedra on the Kuhn triangulation of every
+ * lattice cell -- six tetrahedra per cell, one per permutation (a, b, c) of the axes, corners c0 = (0,0,0), c1 = c0 + e_a, c2 = c1 +
+ * e_b, c3 = (1,1,1).  The upstream TensoRF exports its mesh with skimage's marching cubes on the host; the reference kept only
+ * the `trimesh:` option block.  lattice: [nx][ny][nz] fp32, z fastest (what getDenseAlpha returns); a point is inside iff its
+ * value > level, so a NaN is outside.  Every tetrahedron edge is owned by its lower lattice point p and is one of seven kinds,
+ * bits 0..6 = +x, +y, +z, +x+y, +x+z, +y+z, +x+y+z.  Two passes, no atomics, the same bits on every run:
+ *   jt_mesh_count: edge_flags[p] bit k = owned edge k exists (its upper end is a lattice point) and its ends differ in `inside`
+ *     (popcount = the vertices p owns); tri_count[p] (0..12) = triangles of the cell whose minimum corner is p, 0 without a cell.
+ *   the caller scans both exclusively into int64 (vert_offset[p], tri_offset[p]) and reads the two totals;
+ *   jt_mesh_emit: vertex vert_offset[p] + popcount(edge_flags[p] & ((1 << k) - 1)) lies on owned edge k of p at P(a) + t (P(b) -
+ *     P(a)) per axis, a the owner, b the upper end, t = (level - v_a) / (v_b - v_a) in fp32 clamped to [0, 1] (a NaN t is 0.5),
+ *     P_axis(i) = lo (1 - s) + hi s with s = float(i) / float(n - 1); lo3 / hi3 are HOST pointers.  The triangles of cell p start
+ *     at tri_offset[p], tetrahedra in the order of the permutations (012, 021, 102, 120, 201, 210); two inside corners I0 < I1
+ *     and outside corners O0 < O1 make the quad a = (I0,O0), b = (I0,O1), c = (I1,O1), d = (I1,O0), split along a-c.  The
+ *     winding comes from the case and the permutation's parity alone, normals (right-hand rule) from inside to outside.
+ * vertices [n_vertices][3] fp32, triangles [n_triangles][3] int32 vertex ids.  One launch each on `stream`, nothing else.
+ * JT_ERR_ARG for a NULL pointer, any n < 2 or a non-finite level; JT_ERR_UNSUPPORTED when nx ny nz > 2^27 or when n_vertices
+ * or 3 n_triangles reaches 2^31; n_vertices == 0 launches nothing (vertices / triangles may then be NULL) and is JT_OK.  Stores
+ * past n_vertices / n_triangles are dropped, whatever the offsets say. */
+int jt_mesh_count(const float* lattice, int nx, int ny, int nz, float level, uint8_t* edge_flags, uint8_t* tri_count,
+                  void* stream);
+int jt_mesh_emit(const float* lattice, int nx, int ny, int nz, float level, const float* lo3, const float* hi3,
+                 const uint8_t* edge_flags, const int64_t* vert_offset, const int64_t* tri_offset, long n_vertices,
+                 long n_triangles, float* vertices, int32_t* triangles, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,81 @@
+"""`python -m joint_tensorf_amd.export --yaml=NAME --load=CKPT --output_path=OUT [--mesh.res=N | --mesh.res=[nx,ny,nz]]
+[--mesh.level=0.005] [--mesh.cap=true] [--data.root=DIR --data.scene=lego ...]`: the trained field of a checkpoint as a triangle
+mesh, OUT/mesh.ply (binary little-endian PLY), extracted on the device (Model.export_scene -> extract_mesh ->
+csrc/jt_mesh.hip), and -- when the run's image set is given -- OUT/cameras.json: the refined cameras in the frame the mesh lives
+in, their intrinsics, and the similarity transform to the dataset's frame.  What the upstream TensoRF calls --export_mesh; the
+reference dropped the code and kept the option block.
+
+The joint pose / field optimisation recovers the scene in the frame of the OPTIMISED poses, which differs from the dataset's by
+a similarity transform: geometry is only usable together with the cameras of that same frame.  For `camera.ndc: true` (LLFF)
+the field lives in the scene box's NDC coordinates and so does the mesh; the PLY comment and the JSON say `space ndc`.
+
+Every other `--key.sub=value` is one of the dotted overrides of joint_tensorf_amd.train."""
+import sys
+
+import torch
+
+MESH_DEFAULTS = dict(res=None, level=0.005, cap=True)
+
+
+def build_options(argv):
+    from .options import Opt, apply_overrides, load_options, parse_overrides
+    over = parse_overrides(argv)
+    name = over.pop("yaml", None)
+    if not isinstance(name, str):
+        raise SystemExit("usage: python -m joint_tensorf_amd.export --yaml=NAME --load=CKPT --output_path=OUT [--mesh.res=N] "
+                         "[--mesh.level=L] [--mesh.cap=true|false] [--data.root=DIR --key.sub=value ...]")
+    mesh = over.pop("mesh", None)
+    if mesh is not None and not isinstance(mesh, dict):
+        raise SystemExit("--mesh takes sub-keys: --mesh.res, --mesh.level, --mesh.cap")
+    opt = apply_overrides(load_options(name), over)
+    opt.mesh = Opt(MESH_DEFAULTS)
+    for k, v in (mesh or {}).items():
+        if k not in MESH_DEFAULTS:
+            raise KeyError("unknown option --mesh.%s (known: %s)" % (k, ", ".join(sorted(MESH_DEFAULTS))))
+        opt.mesh[k] = v
+    res = opt.mesh.res
+    if res is not None:
+        res = [res] * 3 if not isinstance(res, list) else res
+        if len(res) != 3 or any(float(v) != int(v) or int(v) < 2 for v in res):
+            raise SystemExit("--mesh.res is one integer or three, each at least 2 (got %r)" % (opt.mesh.res,))
+        opt.mesh.res = [int(v) for v in res]
+    opt.mesh.level = float(opt.mesh.level)
+    if not isinstance(opt.mesh.cap, bool):
+        raise SystemExit("--mesh.cap is true or false (got %r)" % (opt.mesh.cap,))
+    if "device" not in opt:
+        opt.device = "cuda:0"
+    opt.H, opt.W = (int(v) for v in opt.data.image_size)
+    return opt
+
+
+def has_dataset(opt):
+    """whether the run names an image set (a root for the native loaders, a synthetic scene, or ready-made views)"""
+    d = opt.data
+    return bool(d.get("root", None) or d.get("synthetic", False) or d.get("train_views", None) is not None)
+
+
+def main(argv=None):
+    """Returns what Model.export_scene returned (paths and counts)."""
+    from . import checkpoint
+    from .model import bat_hip
+    opt = build_options(sys.argv[1:] if argv is None else list(argv))
+    if not opt.get("load", None) or not opt.get("output_path", None):
+        raise SystemExit("--load=CKPT and --output_path=OUT are required: the checkpoint to read, the directory to write to")
+    dev = torch.device(opt.device)
+    with torch.cuda.device(dev):
+        m = bat_hip.Model(opt)
+        if has_dataset(opt):
+            m.load_dataset(opt, eval_split="test", train_split="train")
+            m.build_networks(opt)
+        else:
+            weight = checkpoint._load(opt.load, "cpu")["graph"].get("se3_refine.weight")
+            m.build_networks(opt, n_views=1 if weight is None else int(weight.shape[0]))
+        m.restore_checkpoint(opt)
+        out = m.export_scene(opt, opt.output_path)
+    print("joint_tensorf_amd.export: %d vertices, %d triangles in %s%s"
+          % (out.n_vertices, out.n_triangles, out.mesh, "; cameras in %s" % out.cameras if out.cameras else ""), flush=True)
+    return out
+
+
+if __name__ == "__main__":
+    main()

@@ -1065,6 +1065,41 @@ class Model(torch.nn.Module):
         eval_io.encode_videos(opt.output_path, novel_path, it=it)
         return None
 
+    # ---- geometry export (the upstream TensoRF's --export_mesh; the reference kept only its option block) ---------
+    @torch.no_grad()
+    def export_scene(self, opt, directory):
+        """<directory>/mesh.ply: the surface {one-step opacity = opt.mesh.level} of the field (TensorVMSplit.extract_mesh on an
+        opt.mesh.res lattice, capped at the scene box unless opt.mesh.cap is false), in the frame of the OPTIMISED cameras -- the
+        scene box's NDC coordinates for opt.camera.ndc; the PLY comments and the JSON say which.  With a training set loaded
+        also <directory>/cameras.json: for every training view the refined world-to-camera [R | t] of that frame, its
+        intrinsics, the pose carried to the dataset's frame, and the Procrustes sim3 (prealign_cameras) that carries it:
+        centre_dataset = (centre - t1) / s1 @ R^T * s0 + t0.  Returns Opt(mesh, cameras, n_vertices, n_triangles)."""
+        from .. import mesh_io
+        mcfg = opt.get("mesh", None) or {}
+        space = "ndc" if opt.camera.ndc else "world"
+        os.makedirs(directory, exist_ok=True)
+        mesh = self.graph.nerf.tensorf.extract_mesh(res=mcfg.get("res", None), level=float(mcfg.get("level", 0.005)),
+                                                    cap=bool(mcfg.get("cap", True)))
+        out = Opt(mesh=os.path.join(directory, "mesh.ply"), cameras=None, n_vertices=int(mesh.vertices.shape[0]),
+                  n_triangles=int(mesh.triangles.shape[0]))
+        mesh_io.write_ply(out.mesh, mesh.vertices, mesh.triangles, mesh_io.mesh_comments(mesh.level, mesh.shape, mesh.lo, mesh.hi, space))
+        if self.train_data is None:
+            print("joint_tensorf_amd: export_scene without a training set: %s written, the cameras skipped" % out.mesh)
+            return out
+        pose, pose_GT = self.get_all_training_poses(opt)
+        aligned, sim3 = self.prealign_cameras(opt, pose, pose_GT)
+
+        def plain(x):
+            return x.detach().cpu().tolist() if torch.is_tensor(x) else x
+        intr = self.train_data.all.intr
+        cameras = {"space": space, "mesh": "mesh.ply", "image_size": [int(opt.H), int(opt.W)], "n_views": int(pose.shape[0]),
+                   "pose_layout": "world-to-camera [R | t], 3 x 4, in the frame of the mesh",
+                   "sim3": {k: plain(sim3[k]) for k in ("t0", "t1", "s0", "s1", "R")},
+                   "views": [{"idx": i, "pose": plain(pose[i]), "intr": plain(intr[i]), "pose_aligned": plain(aligned[i])}
+                             for i in range(pose.shape[0])]}
+        out.cameras = mesh_io.write_cameras(os.path.join(directory, "cameras.json"), cameras)
+        return out
+
     # ---- evaluation (SURVEY 8(f) N1) ---------------------------------------------------------------------------
     @torch.no_grad()
     def get_all_training_poses(self, opt, pose_GT=None):

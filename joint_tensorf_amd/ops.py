@@ -1508,6 +1508,72 @@ def dense_alpha(cfg, density_plane, density_line, xyz, length):
     return out
 
 
+def _byte_popcount(x):
+    """bits set in every byte of a uint8 tensor, as uint8 (three element-wise folds: no [N] gather index)"""
+    x = (x & 0x55) + ((x >> 1) & 0x55)
+    x = (x & 0x33) + ((x >> 2) & 0x33)
+    return (x & 0x0F) + (x >> 4)
+
+
+def mesh_count(vol, level):
+    """jt_mesh_count on a lattice vol [nx, ny, nz] fp32: (edge_flags [N] uint8, tri_count [N] uint8), one launch"""
+    if vol.dim() != 3 or vol.dtype != torch.float32 or not vol.is_contiguous():
+        raise ValueError("mesh_from_lattice: the lattice must be contiguous fp32 [nx, ny, nz] (got %s %s)" % (vol.dtype, tuple(vol.shape)))
+    nx, ny, nz = vol.shape
+    flags = torch.empty(vol.numel(), device=vol.device, dtype=torch.uint8)
+    tris = torch.empty(vol.numel(), device=vol.device, dtype=torch.uint8)
+    check(lib.jt_mesh_count(ptr(vol), nx, ny, nz, float(level), ptr(flags), ptr(tris), _stream()), "jt_mesh_count")
+    return flags, tris
+
+
+def mesh_offsets(flags, tris):
+    """the caller's scan between the two passes: (vert_offset [N] int64, tri_offset [N] int64, totals [2] int64 = (n_vertices,
+    n_triangles)), all on the device -- no host read"""
+    verts = _byte_popcount(flags)
+    vert_end = torch.cumsum(verts, 0, dtype=torch.int64)
+    tri_end = torch.cumsum(tris, 0, dtype=torch.int64)
+    totals = torch.stack([vert_end[-1], tri_end[-1]])
+    return vert_end.sub_(verts), tri_end.sub_(tris), totals
+
+
+def mesh_emit(vol, level, lo, hi, flags, vert_offset, tri_offset, nv, nt):
+    """jt_mesh_emit: (vertices [nv, 3] fp32, triangles [nt, 3] int32); nothing is launched for an empty mesh"""
+    vertices = torch.empty(nv, 3, device=vol.device, dtype=torch.float32)
+    triangles = torch.empty(nt, 3, device=vol.device, dtype=torch.int32)
+    if nv:
+        nx, ny, nz = vol.shape
+        check(lib.jt_mesh_emit(ptr(vol), nx, ny, nz, float(level), (ctypes.c_float * 3)(*lo), (ctypes.c_float * 3)(*hi), ptr(flags),
+                               ptr(vert_offset), ptr(tri_offset), nv, nt, ptr(vertices), ptr(triangles), _stream()),
+              "jt_mesh_emit")
+    return vertices, triangles
+
+
+def mesh_from_lattice(vol, level, lo, hi):
+    """The iso-surface {vol = level} of a lattice vol [nx, ny, nz] fp32 (z fastest, as getDenseAlpha returns it) over the box lo
+    .. hi (three floats each) as a triangle mesh on the device: vertices [nv, 3] fp32, triangles [nt, 3] int32, normals
+    (right-hand rule) from inside (vol > level) to outside.  Marching tetrahedra on the Kuhn triangulation (csrc/jt_mesh.hip):
+    jt_mesh_count, two cumsums, ONE host read of the two totals, jt_mesh_emit.  No atomics: the order of vertices and
+    triangles is a function of the lattice alone, two calls return the same bits.  Empty results are [0, 3] tensors."""
+    lo = [float(v) for v in (lo.tolist() if torch.is_tensor(lo) else lo)]
+    hi = [float(v) for v in (hi.tolist() if torch.is_tensor(hi) else hi)]
+    if len(lo) != 3 or len(hi) != 3:
+        raise ValueError("mesh_from_lattice: lo and hi are three floats each")
+    vol = vol.detach().contiguous()
+    flags, tris = mesh_count(vol, level)
+    vert_offset, tri_offset, totals = mesh_offsets(flags, tris)
+    nv, nt = (int(v) for v in totals.tolist())
+    return mesh_emit(vol, level, lo, hi, flags, vert_offset, tri_offset, nv, nt)
+
+
+def cap_lattice(vol, lo, hi):
+    """One layer of zeros round a lattice and the box grown by one lattice spacing per side (fp32 arithmetic on the host): a
+    surface {vol = level > 0} that reaches the box is closed there.  Returns (padded lattice, lo, hi)."""
+    shape = torch.tensor(list(vol.shape), dtype=torch.float32)
+    lo, hi = torch.as_tensor(lo, dtype=torch.float32).cpu().reshape(3), torch.as_tensor(hi, dtype=torch.float32).cpu().reshape(3)
+    unit = (hi - lo) / (shape - 1)
+    return torch.nn.functional.pad(vol, (1, 1, 1, 1, 1, 1)), (lo - unit).tolist(), (hi + unit).tolist()
+
+
 def blur_images(images, taps):
     """Separable replicate-padded blur (along W, then H) of a batch of images [n, c, H, W] with one tap vector:
     the 2-D GT blur of nerf.Model.process_GT_images (model/nerf.py:98-110) on the factor-blur kernel.  All n*c

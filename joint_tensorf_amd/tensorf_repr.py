@@ -6,6 +6,7 @@ What stays host-side torch here is orchestration the reference also does on the 
 from a schedule scalar, regularisers over the parameters, grid upsampling); everything per-ray /
 per-sample runs in joint_tensorf_amd/csrc.
 """
+import collections
 import math
 
 import numpy as np
@@ -16,6 +17,9 @@ from . import _lib, ops
 
 MAT_MODE = ops.MAT_MODE
 VEC_MODE = ops.VEC_MODE
+
+# what extract_mesh returns: the arrays on the device, and the lattice they were taken on (box, points per axis, iso-level)
+Mesh = collections.namedtuple("Mesh", "vertices triangles lo hi shape level")
 
 
 def _channel_last_param(t):
@@ -288,6 +292,59 @@ class BAT_VMSplit(torch.nn.Module):
         dense_xyz = aabb[0] * (1 - samples) + aabb[1] * samples
         alpha = self.compute_alpha(dense_xyz.view(-1, 3), self.stepSize).view(*gridSize)
         return alpha, dense_xyz
+
+    @staticmethod
+    def _mesh_resolution(res, grid):
+        if res is None:
+            return [int(v) for v in grid]
+        if isinstance(res, (int, np.integer)):
+            return [int(res)] * 3
+        res = [int(v) for v in res]
+        if len(res) != 3:
+            raise ValueError("extract_mesh: res is None (the factor grid), one int or three (got %r)" % (res,))
+        return res
+
+    @torch.no_grad()
+    def dense_alpha_lattice(self, res=None, slab_points=1 << 24):
+        """getDenseAlpha(res)[0] to the bit, [nx, ny, nz] fp32, evaluated in slabs of at most `slab_points` points whose coordinates
+        are formed on the device by getDenseAlpha's own expression: no [N, 3] tensor on the host, none of full size on the device."""
+        n = self._mesh_resolution(res, self.gridSize.tolist())
+        slab_points = int(slab_points)
+        if min(n) < 2 or slab_points < 1:
+            raise ValueError("extract_mesh: at least two lattice points per axis and a positive slab (got %r, %r)" % (n, slab_points))
+        dev = self.density_plane[0].device
+        aabb = self.aabb.to(dev)
+        # per axis what getDenseAlpha evaluates per point: linspace on the host, then aabb[0] * (1 - s) + aabb[1] * s on the device
+        axes = []
+        for a in range(3):
+            s = torch.linspace(0, 1, n[a]).to(dev)
+            axes.append(aabb[0, a] * (1 - s) + aabb[1, a] * s)
+        total = n[0] * n[1] * n[2]
+        vol = torch.empty(total, device=dev, dtype=torch.float32)
+        for start in range(0, total, slab_points):
+            idx = torch.arange(start, min(start + slab_points, total), device=dev)
+            r = torch.div(idx, n[2], rounding_mode="floor")
+            xyz = torch.stack([axes[0][torch.div(r, n[1], rounding_mode="floor")], axes[1][r % n[1]], axes[2][idx % n[2]]], -1)
+            vol[start:start + idx.numel()] = self.compute_alpha(xyz, self.stepSize)
+        return vol.view(*n)
+
+    @torch.no_grad()
+    def extract_mesh(self, res=None, level=0.005, cap=True, slab_points=1 << 24):
+        """The surface {one-step opacity = level} of the field as a triangle mesh, extracted on the device (ops.mesh_from_lattice):
+        a Mesh of vertices [nv, 3] fp32 in the scene box's coordinates, triangles [nt, 3] int32 with normals pointing out of the
+        opaque side, and the box (lo, hi), the size (shape) and the level of the lattice the surface was taken on.  What the
+        upstream TensoRF's --export_mesh does with getDenseAlpha and a host marching cubes.
+
+        res: None (the factor grid), an int or three -- lattice points per axis; the lattice is dense_alpha_lattice(res,
+        slab_points), with the blur state the last forward left, as compute_alpha (a freshly restored checkpoint has none).
+        cap: one layer of zeros round the lattice and the box grown by one lattice spacing per side, so that a surface reaching
+        the scene box is closed there.  level = 0.005 is the upstream export's."""
+        vol = self.dense_alpha_lattice(res, slab_points)
+        lo, hi = self.aabb[0].tolist(), self.aabb[1].tolist()
+        if cap:
+            vol, lo, hi = ops.cap_lattice(vol, lo, hi)
+        vertices, triangles = ops.mesh_from_lattice(vol, level, lo, hi)
+        return Mesh(vertices, triangles, tuple(lo), tuple(hi), tuple(vol.shape), float(level))
 
     @torch.no_grad()
     def updateAlphaMask(self, gridSize=(200, 200, 200)):
