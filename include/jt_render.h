@@ -39,9 +39,10 @@ extern "C" {
  * jt_shade_lean_tape / jt_shade_set_lean_tape, the workspace no longer carries the tile lists unless that variant is selected;
  * 1201: + jt_chip_geometry; 1202: + jt_shade_workspace_layout; 1203: + jt_march_forward_pose / jt_march_backward_pose; 1204: +
  * jt_lattice_indices; 1205: + jt_ssim_forward / jt_ssim_workspace_bytes; 1206: +
- * jt_image_ingest / jt_image_ingest_workspace_bytes; 1207: + jt_shade_backward_plan / jt_march_backward_plan; 1208: + jt_mesh_count / jt_mesh_emit.  Additions bump the last two digits, anything a caller built against the old header would get wrong bumps the
+ * jt_image_ingest / jt_image_ingest_workspace_bytes; 1207: + jt_shade_backward_plan / jt_march_backward_plan; 1208: + jt_mesh_count / jt_mesh_emit;
+ * 1209: + jt_components_init / jt_components_sweep / jt_component_sizes, jt_density_gradient, JT_COMPONENTS_TILE.  Additions bump the last two digits, anything a caller built against the old header would get wrong bumps the
  * hundreds). */
-#define JT_VERSION 1208
+#define JT_VERSION 1209
 
 #define JT_OK 0
 #define JT_ERR_ARG 1         /* null pointer / bad size */
@@ -212,6 +213,12 @@ int jt_blur_batch_backward(const JtBlurItem* items, int n_items, void* stream);
  * Replaces BatBase.compute_alpha (batBase.py:27-41) under TensorBase.getDenseAlpha (tensorBase.py:618-634). */
 int jt_dense_alpha(const JtScene* scene, const JtFactors* factors, const float* xyz, long n, float length,
                    float* alpha, void* stream);
+/* Density feature and its WORLD-space gradient at n arbitrary world points xyz [n][3]: feat [n] (may be NULL) = the feature
+ * before the shift and the activation, grad [n][3] = d feat / d xyz = (d feat / d normalised coordinate) * 2 / (hi - lo) per
+ * axis.  The field of the factors themselves: the alpha mask is ignored, and a point beyond the box meets grid_sample's zero
+ * padding (taps outside a factor count as zero values, the fractional weights stay).  One thread per point, one launch. */
+int jt_density_gradient(const JtScene* scene, const JtFactors* factors, const float* xyz, long n, float* feat, float* grad,
+                        void* stream);
 int jt_march_forward(const JtScene* scene, const JtFactors* factors, const float* rays_o, const float* rays_d,
                      const float* jitter, const float* zvals, int n_rays, float* sigma_feat, float* weight,
                      float* tmin, int32_t* shade_count, int32_t* shade_offset, uint16_t* shade_idx,
@@ -599,6 +606,27 @@ int jt_mesh_count(const float* lattice, int nx, int ny, int nz, float level, uin
 int jt_mesh_emit(const float* lattice, int nx, int ny, int nz, float level, const float* lo3, const float* hi3,
                  const uint8_t* edge_flags, const int64_t* vert_offset, const int64_t* tri_offset, long n_vertices,
                  long n_triangles, float* vertices, int32_t* triangles, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Connected components of a lattice's inside points (csrc/jt_components.hip), with the connectivity of the mesh above: two
+ * points are adjacent iff both are inside (value > level; a NaN is outside) and they differ by + or - one of the seven edge
+ * kinds -- 14 neighbours; (+x, -y) is no edge.  Every tetrahedron's inside corners then lie in one component, and the surface
+ * splits exactly along components.  labels [nx][ny][nz] int32, z fastest: -1 outside, else the SMALLEST flat index of the
+ * point's component -- a function of the lattice alone, the same bits on every run.
+ *   jt_components_init: labels[p] = p inside, -1 outside.
+ *   jt_components_sweep: one sweep of min-label propagation; a workgroup owns a tile of JT_COMPONENTS_TILE^3 points, lowers
+ *     its labels over the 14 neighbours (a one-point halo read from its neighbours' tiles) until the tile is stable and stores
+ *     only into its own tile; *lowered (a device word, zeroed by the caller) is set to 1 when any label fell.  With jump != 0 a
+ *     second launch follows: labels[p] = labels[labels[...]] down the chain.  No workgroup waits for another: a halo word a
+ *     neighbour lowers during the same launch may or may not be seen.  The caller repeats until a sweep leaves *lowered at 0;
+ *     the labels are then final (and only then).
+ *   jt_component_sizes: sizes[l] += 1 for every point with label l >= 0; sizes [nx ny nz] int32, zeroed by the caller
+ *     (integer atomics: the sums do not depend on the order).
+ * JT_ERR_ARG for a NULL pointer, any n < 2 or a non-finite level; JT_ERR_UNSUPPORTED when nx ny nz > 2^27. */
+#define JT_COMPONENTS_TILE 8
+int jt_components_init(const float* lattice, int nx, int ny, int nz, float level, int32_t* labels, void* stream);
+int jt_components_sweep(int32_t* labels, int nx, int ny, int nz, int32_t* lowered, int jump, void* stream);
+int jt_component_sizes(const int32_t* labels, int nx, int ny, int nz, int32_t* sizes, void* stream);
 
 #ifdef __cplusplus
 }

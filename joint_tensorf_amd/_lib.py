@@ -136,8 +136,12 @@ SIGNATURES = {
     "jt_adam_step_coefs": (I, [P, I, F, F, F, P, P]),
     "jt_poke": (I, [P, P, I, P]),
     "jt_dense_alpha": (I, [SP, FP, P, ctypes.c_long, F, P, P]),
+    "jt_density_gradient": (I, [SP, FP, P, ctypes.c_long, P, P, P]),
     "jt_mesh_count": (I, [P, I, I, I, F, P, P, P]),
     "jt_mesh_emit": (I, [P, I, I, I, F, P, P, P, P, P, ctypes.c_long, ctypes.c_long, P, P, P]),
+    "jt_components_init": (I, [P, I, I, I, F, P, P]),
+    "jt_components_sweep": (I, [P, I, I, I, P, I, P]),
+    "jt_component_sizes": (I, [P, I, I, I, P, P]),
     "jt_blur_batch_forward": (I, [P, I, P]),
     "jt_blur_batch_backward": (I, [P, I, P]),
     "jt_factor_reg_forward": (I, [P, I, I, I, P, P]),
@@ -180,7 +184,7 @@ def fused_lib():
 # the JT_VERSION of include/jt_render.h that SIGNATURES and the struct mirrors above were written against.  A constant, not a
 # read of the header at import time: a vendored copy of the package has no include/ directory beside it (tests/test_abi.py
 # holds this number, the header's and the library's together)
-JT_ABI_VERSION = 1208
+JT_ABI_VERSION = 1209
 
 
 def header_version():

@@ -207,11 +207,16 @@ struct Axis {
   float scale;   // d(ix)/d(normalised coord) = (size-1)/2
 };
 
+// ROUNDED: the fraction of the ROUNDED product ix, the value tests/pinned_ref.py pins (ix - fl is then exact).  The default
+// leaves the subtraction to the compiler, which contracts the product into it: the fraction of the unrounded product, up to
+// half an ulp of ix away.  The render kernels keep the default (their results are held at tolerances far above that); a
+// kernel whose OUTPUT is the interpolated value itself (k_density_gradient) asks for the pinned one.
+template <bool ROUNDED = false>
 __device__ inline Axis axis_taps(float g, int size) {
   Axis a;
   float ix = ((g + 1.f) * 0.5f) * (float)(size - 1);
   float fl = floorf(ix);
-  a.f = ix - fl;
+  a.f = ROUNDED ? add_rn(ix, -fl) : ix - fl;
   a.i0 = (int)fl;
   bool in0 = (a.i0 >= 0) && (a.i0 < size);
   bool in1 = (a.i0 + 1 >= 0) && (a.i0 + 1 < size);
@@ -231,10 +236,11 @@ struct PlaneTaps {
   Axis ax, ay;
 };
 
+template <bool ROUNDED = false>
 __device__ inline PlaneTaps plane_taps(float gx, float gy, int H, int W, int C) {
   PlaneTaps t;
-  t.ax = axis_taps(gx, W);
-  t.ay = axis_taps(gy, H);
+  t.ax = axis_taps<ROUNDED>(gx, W);
+  t.ay = axis_taps<ROUNDED>(gy, H);
   t.o00 = (t.ay.c0 * W + t.ax.c0) * C;
   t.o10 = (t.ay.c0 * W + t.ax.c1) * C;
   t.o01 = (t.ay.c1 * W + t.ax.c0) * C;

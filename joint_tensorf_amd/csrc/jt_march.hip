@@ -79,15 +79,17 @@ __device__ inline void density_feature_grad(const Dev& D, const float n[3], floa
 }
 
 // density feature AND its coordinate gradient from one gather of the taps (the forward march of a pose-only render: the backward
-// then needs no second walk over the density factors) -- density_feature's sum and density_feature_grad's sums, term by term
+// then needs no second walk over the density factors) -- density_feature's sum and density_feature_grad's sums, term by term.
+// ROUNDED: the tap fractions of axis_taps<true> (jt_common.h); the march keeps the default, like density_feature beside it.
+template <bool ROUNDED = false>
 __device__ inline float density_feature_with_grad(const Dev& D, const float n[3], float gn[3]) {
   gn[0] = gn[1] = gn[2] = 0.f;
   float feat = 0.f;
   const int C = D.Cd;
 #pragma unroll
   for (int i = 0; i < 3; ++i) {
-    const PlaneTaps t = plane_taps(n[kM0(i)], n[kM1(i)], D.ph[i], D.pw[i], C);
-    const Axis l = axis_taps(n[kV(i)], D.ll[i]);
+    const PlaneTaps t = plane_taps<ROUNDED>(n[kM0(i)], n[kM1(i)], D.ph[i], D.pw[i], C);
+    const Axis l = axis_taps<ROUNDED>(n[kV(i)], D.ll[i]);
     const float* P = D.dP[i];
     const float* L = D.dL[i];
     const int l0 = l.c0 * C, l1 = l.c1 * C;
@@ -828,6 +830,23 @@ __global__ __launch_bounds__(256) void k_dense_alpha(Dev D, const float* __restr
   alpha[i] = 1.f - expf(-sigma * length);
 }
 
+// density feature (before the shift and the activation) and its WORLD-space gradient at arbitrary points: the surface normal
+// of an exported mesh is -grad / |grad|.  The field of the factors themselves: the alpha mask is not consulted, and a point
+// beyond the box meets grid_sample's zero padding, as in density_feature_grad.  d n[a] / d p[a] = D.inv[a] (normalize).
+__global__ __launch_bounds__(256) void k_density_gradient(Dev D, const float* __restrict__ xyz, long n, float* __restrict__ feat,
+                                                          float* __restrict__ grad) {
+  const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float p[3] = {xyz[i * 3], xyz[i * 3 + 1], xyz[i * 3 + 2]};
+  float nrm[3], gn[3];
+  normalize(D, p, nrm);
+  // the value itself is this kernel's output: the tap fractions of the rounded texel coordinate, which the fp64 reference pins
+  const float f = density_feature_with_grad<true>(D, nrm, gn);
+  if (feat) feat[i] = f;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) grad[i * 3 + a] = gn[a] * D.inv[a];
+}
+
 }  // namespace jt
 
 using namespace jt;
@@ -911,6 +930,22 @@ extern "C" int jt_dense_alpha(const JtScene* scene, const JtFactors* factors, co
   if (n == 0) return JT_OK;
   hipLaunchKernelGGL(k_dense_alpha, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, D, xyz, n,
                      length, alpha);
+  JT_LAUNCH_CHECK();
+  return JT_OK;
+}
+
+extern "C" int jt_density_gradient(const JtScene* scene, const JtFactors* factors, const float* xyz, long n, float* feat,
+                                   float* grad, void* stream) {
+  Dev D;
+  int rc = make_dev(scene, factors, &D);
+  if (rc) return rc;
+  if (!factors || !xyz || !grad || n < 0) return JT_ERR_ARG;
+  if ((rc = check_density_shape(D))) return rc;
+  for (int a = 0; a < 3; ++a)
+    if (!D.dP[a] || !D.dL[a]) return JT_ERR_ARG;
+  if (n == 0) return JT_OK;
+  hipLaunchKernelGGL(k_density_gradient, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, D, xyz, n, feat,
+                     grad);
   JT_LAUNCH_CHECK();
   return JT_OK;
 }

@@ -9,30 +9,58 @@ The joint pose / field optimisation recovers the scene in the frame of the OPTIM
 a similarity transform: geometry is only usable together with the cameras of that same frame.  For `camera.ndc: true` (LLFF)
 the field lives in the scene box's NDC coordinates and so does the mesh; the PLY comment and the JSON say `space ndc`.
 
+`--surface.keep_largest=K` / `--surface.min_points=M` remove floaters before a triangle is emitted: the connected components of
+the opacity lattice (csrc/jt_components.hip, the mesh's own connectivity) of which only the K largest, of at least M lattice
+points, stay.  `--surface.normals=true` writes per-vertex normals (the normalised negative density gradient),
+`--surface.colors=true` per-vertex colours (the appearance branch at the vertex, seen against its normal).  Without a
+`--surface.*` option mesh.ply holds positions and triangles only.
+
 Every other `--key.sub=value` is one of the dotted overrides of joint_tensorf_amd.train."""
 import sys
 
 import torch
 
 MESH_DEFAULTS = dict(res=None, level=0.005, cap=True)
+# what is done to the surface beyond extracting it: floaters removed by connected component (keep the K largest, drop those of
+# fewer than M lattice points), per-vertex normals (the density gradient) and colours (the appearance branch seen head-on)
+SURFACE_DEFAULTS = dict(keep_largest=None, min_points=None, normals=False, colors=False)
+
+
+def _option_group(over, name, defaults):
+    """pop the dotted group --NAME.* from the overrides: Opt(defaults) with the given sub-keys; an unknown one is a KeyError"""
+    from .options import Opt
+    given = over.pop(name, None)
+    if given is not None and not isinstance(given, dict):
+        raise SystemExit("--%s takes sub-keys: %s" % (name, ", ".join("--%s.%s" % (name, k) for k in defaults)))
+    group = Opt(defaults)
+    for k, v in (given or {}).items():
+        if k not in defaults:
+            raise KeyError("unknown option --%s.%s (known: %s)" % (name, k, ", ".join(sorted(defaults))))
+        group[k] = v
+    return group
 
 
 def build_options(argv):
-    from .options import Opt, apply_overrides, load_options, parse_overrides
+    from .options import apply_overrides, load_options, parse_overrides
     over = parse_overrides(argv)
     name = over.pop("yaml", None)
     if not isinstance(name, str):
         raise SystemExit("usage: python -m joint_tensorf_amd.export --yaml=NAME --load=CKPT --output_path=OUT [--mesh.res=N] "
-                         "[--mesh.level=L] [--mesh.cap=true|false] [--data.root=DIR --key.sub=value ...]")
-    mesh = over.pop("mesh", None)
-    if mesh is not None and not isinstance(mesh, dict):
-        raise SystemExit("--mesh takes sub-keys: --mesh.res, --mesh.level, --mesh.cap")
+                         "[--mesh.level=L] [--mesh.cap=true|false] [--surface.keep_largest=K] [--surface.min_points=M] "
+                         "[--surface.normals=true|false] [--surface.colors=true|false] [--data.root=DIR --key.sub=value ...]")
+    mesh = _option_group(over, "mesh", MESH_DEFAULTS)
+    surface = _option_group(over, "surface", SURFACE_DEFAULTS)
     opt = apply_overrides(load_options(name), over)
-    opt.mesh = Opt(MESH_DEFAULTS)
-    for k, v in (mesh or {}).items():
-        if k not in MESH_DEFAULTS:
-            raise KeyError("unknown option --mesh.%s (known: %s)" % (k, ", ".join(sorted(MESH_DEFAULTS))))
-        opt.mesh[k] = v
+    opt.mesh, opt.surface = mesh, surface
+    for k in ("keep_largest", "min_points"):
+        v = surface[k]
+        if v is not None:
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or float(v) != int(v) or int(v) < 1:
+                raise SystemExit("--surface.%s is a positive integer (got %r)" % (k, v))
+            surface[k] = int(v)
+    for k in ("normals", "colors"):
+        if not isinstance(surface[k], bool):
+            raise SystemExit("--surface.%s is true or false (got %r)" % (k, surface[k]))
     res = opt.mesh.res
     if res is not None:
         res = [res] * 3 if not isinstance(res, list) else res

@@ -1,7 +1,7 @@
 """Triangle meshes and camera sets on disk: what `python -m joint_tensorf_amd.export` leaves behind.
 
 PLY, binary little-endian 1.0, the layout every mesh tool reads:
-    element vertex N:  property float x / y / z
+    element vertex N:  property float x / y / z  [property float nx / ny / nz]  [property uchar red / green / blue]
     element face M:    property list uchar int vertex_indices     (a count byte 3 and three int32 per triangle)
 `comments` go into the header as `comment ...` lines (one line each, ASCII); the exporter records the iso-level, the lattice size,
 the box and `space world|ndc` there.  Host code in NumPy: a file write is not a hot path."""
@@ -16,12 +16,49 @@ def _host(a):
     return a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
 
 
-def write_ply(path, vertices, triangles, comments=()):
-    """vertices [nv, 3] floats, triangles [nt, 3] integers (tensors or arrays; either may be empty).  Returns the path."""
+_VERTEX_PROPS = ["property float x", "property float y", "property float z"]
+_NORMAL_PROPS = ["property float nx", "property float ny", "property float nz"]
+_COLOR_PROPS = ["property uchar red", "property uchar green", "property uchar blue"]
+
+
+def quantise_colors(colors):
+    """colours [n, 3] in [0, 1] -> uint8 floor(255 c + 0.5), clamped to 0 .. 255; a NaN is refused"""
+    C = np.asarray(_host(colors), dtype=np.float64).reshape(-1, 3)
+    if np.isnan(C).any():
+        raise ValueError("write_ply: a colour is NaN")
+    return np.clip(np.floor(255.0 * C + 0.5), 0, 255).astype(np.uint8)
+
+
+def _vertex_dtype(normals, colors):
+    fields = [("p", "<f4", (3,))]
+    if normals:
+        fields.append(("n", "<f4", (3,)))
+    if colors:
+        fields.append(("c", "u1", (3,)))
+    return np.dtype(fields)                                  # packed: 12, 24, 15 or 27 bytes per vertex
+
+
+def write_ply(path, vertices, triangles, comments=(), normals=None, colors=None):
+    """vertices [nv, 3] floats, triangles [nt, 3] integers (tensors or arrays; either may be empty); optionally per vertex
+    normals [nv, 3] floats (`float nx ny nz`) and colors [nv, 3] in [0, 1] (`uchar red green blue`, quantise_colors).
+    Returns the path."""
     V = np.ascontiguousarray(_host(vertices).reshape(-1, 3), dtype="<f4")
     T = _host(triangles).reshape(-1, 3)
     if len(T) and (T.min() < 0 or T.max() >= len(V)):
         raise ValueError("write_ply: a triangle names vertex %d of %d" % (int(T.max() if T.max() >= len(V) else T.min()), len(V)))
+    props = list(_VERTEX_PROPS)
+    if normals is not None or colors is not None:
+        rows = np.empty(len(V), dtype=_vertex_dtype(normals is not None, colors is not None))
+        rows["p"] = V
+        for name, a, plist in (("n", normals, _NORMAL_PROPS), ("c", colors, _COLOR_PROPS)):
+            if a is None:
+                continue
+            a = quantise_colors(a) if name == "c" else np.asarray(_host(a), dtype="<f4").reshape(-1, 3)
+            if len(a) != len(V):
+                raise ValueError("write_ply: %d vertices, %d rows of %s" % (len(V), len(a), "colors" if name == "c" else "normals"))
+            rows[name] = a
+            props += plist
+        V = rows
     faces = np.empty(len(T), dtype=_FACE)
     faces["n"] = 3
     faces["v"] = T
@@ -31,8 +68,8 @@ def write_ply(path, vertices, triangles, comments=()):
         if "\n" in c or "\r" in c or not c.isascii():
             raise ValueError("write_ply: a comment is one ASCII line (got %r)" % c)
         lines.append("comment " + c)
-    lines += ["element vertex %d" % len(V), "property float x", "property float y", "property float z",
-              "element face %d" % len(T), "property list uchar int vertex_indices", "end_header"]
+    lines += ["element vertex %d" % len(V)] + props + ["element face %d" % len(T), "property list uchar int vertex_indices",
+                                                       "end_header"]
     with open(path, "wb") as f:
         f.write(("\n".join(lines) + "\n").encode("ascii"))
         f.write(V.tobytes())
@@ -65,6 +102,45 @@ def read_ply(path):
     if nt and not (faces["n"] == 3).all():
         raise ValueError("%s: a face that is not a triangle" % path)
     return V, np.ascontiguousarray(faces["v"], dtype=np.int32).reshape(nt, 3), comments
+
+
+def read_ply_attributes(path):
+    """A file write_ply wrote, in any of its four vertex layouts (plain, + normals, + colours, + both) -> dict(vertices [nv, 3]
+    float32, triangles [nt, 3] int32, comments: list of str, normals [nv, 3] float32 or None, colors [nv, 3] uint8 or None)."""
+    with open(path, "rb") as f:
+        data = f.read()
+    end = data.find(b"end_header\n")
+    if not data.startswith(b"ply\n") or end < 0:
+        raise ValueError("%s is not a PLY file" % path)
+    head = data[:end].decode("ascii").split("\n")[1:]
+    body = data[end + len(b"end_header\n"):]
+    if not head or head[0] != "format binary_little_endian 1.0":
+        raise ValueError("%s: only binary little-endian PLY is read" % path)
+    comments = [ln[len("comment "):] for ln in head if ln.startswith("comment ")]
+    rest = [ln for ln in head[1:] if ln and not ln.startswith("comment ")]
+    layouts = [(n, c, _VERTEX_PROPS + (_NORMAL_PROPS if n else []) + (_COLOR_PROPS if c else []))
+               for n in (False, True) for c in (False, True)]
+    match = [(n, c) for n, c, props in layouts if rest[1:-2] == props]
+    if not match:
+        raise ValueError("%s: not a vertex / face layout write_ply writes" % path)
+    has_n, has_c = match[0]
+    try:
+        nv, nt = int(rest[0].split()[2]), int(rest[-2].split()[2])
+    except (IndexError, ValueError):
+        raise ValueError("%s: not a vertex / face layout write_ply writes" % path) from None
+    if rest[0] != "element vertex %d" % nv or rest[-2:] != ["element face %d" % nt, "property list uchar int vertex_indices"]:
+        raise ValueError("%s: not a vertex / face layout write_ply writes" % path)
+    vdt = _vertex_dtype(has_n, has_c)
+    if len(body) != vdt.itemsize * nv + _FACE.itemsize * nt:
+        raise ValueError("%s: %d payload bytes for %d vertices and %d triangles" % (path, len(body), nv, nt))
+    rows = np.frombuffer(body, dtype=vdt, count=nv)
+    faces = np.frombuffer(body, dtype=_FACE, count=nt, offset=vdt.itemsize * nv)
+    if nt and not (faces["n"] == 3).all():
+        raise ValueError("%s: a face that is not a triangle" % path)
+    return dict(vertices=np.ascontiguousarray(rows["p"], dtype=np.float32).reshape(nv, 3),
+                triangles=np.ascontiguousarray(faces["v"], dtype=np.int32).reshape(nt, 3), comments=comments,
+                normals=np.ascontiguousarray(rows["n"], dtype=np.float32).reshape(nv, 3) if has_n else None,
+                colors=np.ascontiguousarray(rows["c"], dtype=np.uint8).reshape(nv, 3) if has_c else None)
 
 
 def mesh_comments(level, shape, lo, hi, space):

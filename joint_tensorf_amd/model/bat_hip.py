@@ -1073,16 +1073,34 @@ class Model(torch.nn.Module):
         scene box's NDC coordinates for opt.camera.ndc; the PLY comments and the JSON say which.  With a training set loaded
         also <directory>/cameras.json: for every training view the refined world-to-camera [R | t] of that frame, its
         intrinsics, the pose carried to the dataset's frame, and the Procrustes sim3 (prealign_cameras) that carries it:
-        centre_dataset = (centre - t1) / s1 @ R^T * s0 + t0.  Returns Opt(mesh, cameras, n_vertices, n_triangles)."""
+        centre_dataset = (centre - t1) / s1 @ R^T * s0 + t0.  opt.surface (keep_largest, min_points, normals, colors; all off
+        when absent) removes floaters and adds per-vertex normals / colours to the PLY, with a `components kept K dropped D`
+        and a `normals degenerate N` comment for what ran.  Returns Opt(mesh, cameras, n_vertices, n_triangles, n_components,
+        n_degenerate_normals); the last two are None for what did not run."""
         from .. import mesh_io
         mcfg = opt.get("mesh", None) or {}
         space = "ndc" if opt.camera.ndc else "world"
         os.makedirs(directory, exist_ok=True)
-        mesh = self.graph.nerf.tensorf.extract_mesh(res=mcfg.get("res", None), level=float(mcfg.get("level", 0.005)),
-                                                    cap=bool(mcfg.get("cap", True)))
+        scfg = opt.get("surface", None) or {}
+        nerf = self.graph.nerf
+        pe = {}
+        if scfg.get("colors", False) and getattr(nerf, "progress_host", None) is not None:
+            # the schedule's PE masks at the model's progress, as render_rays hands them to a forward
+            for key, name in (("view_pe_progress", "c2f_view_pe_schedule"), ("fea_pe_progress", "c2f_fea_pe_schedule")):
+                pe[key] = interp_schedule(nerf.progress_host, opt[name]) if _has(opt, name) else 1.0
+        mesh = nerf.tensorf.extract_mesh(res=mcfg.get("res", None), level=float(mcfg.get("level", 0.005)),
+                                         cap=bool(mcfg.get("cap", True)), keep_largest=scfg.get("keep_largest", None),
+                                         min_points=scfg.get("min_points", None), normals=bool(scfg.get("normals", False)),
+                                         colors=bool(scfg.get("colors", False)), **pe)
         out = Opt(mesh=os.path.join(directory, "mesh.ply"), cameras=None, n_vertices=int(mesh.vertices.shape[0]),
-                  n_triangles=int(mesh.triangles.shape[0]))
-        mesh_io.write_ply(out.mesh, mesh.vertices, mesh.triangles, mesh_io.mesh_comments(mesh.level, mesh.shape, mesh.lo, mesh.hi, space))
+                  n_triangles=int(mesh.triangles.shape[0]), n_components=mesh.n_components,
+                  n_degenerate_normals=mesh.n_degenerate_normals)
+        comments = mesh_io.mesh_comments(mesh.level, mesh.shape, mesh.lo, mesh.hi, space)
+        if mesh.n_components is not None:
+            comments.append("components kept %d dropped %d" % mesh.n_components)
+        if mesh.normals is not None:
+            comments.append("normals degenerate %d" % mesh.n_degenerate_normals)
+        mesh_io.write_ply(out.mesh, mesh.vertices, mesh.triangles, comments, normals=mesh.normals, colors=mesh.colors)
         if self.train_data is None:
             print("joint_tensorf_amd: export_scene without a training set: %s written, the cameras skipped" % out.mesh)
             return out

@@ -1574,6 +1574,136 @@ def cap_lattice(vol, lo, hi):
     return torch.nn.functional.pad(vol, (1, 1, 1, 1, 1, 1)), (lo - unit).tolist(), (hi + unit).tolist()
 
 
+# points per edge of the tile a workgroup of the component sweep owns (include/jt_render.h: JT_COMPONENTS_TILE)
+COMPONENTS_TILE = 8
+# Sweeps after which lattice_components gives up.  Measured with pointer jumping (profiles/mesh_surface_export.txt): the two
+# snakes through 17 x 17 x 9 of tests/test_gpu_components.py converge at sweep 14, the 400^3 blob lattice at sweep 13 (35 and 41
+# without the jumps).  The default is 64 times the larger count rounded up to 16: room for paths far longer than any surface of
+# a trained field winds, and still a bound (0.28 ms per sweep and jump at 400^3: a third of a second).
+COMPONENTS_MAX_SWEEPS = 1024
+# what the last lattice_components call took: sweeps launched, and the first sweep that lowered nothing
+last_components_stats = {}
+
+
+def _lattice_arg(vol, who):
+    if vol.dim() != 3 or vol.dtype != torch.float32 or not vol.is_contiguous():
+        raise ValueError("%s: the lattice must be contiguous fp32 [nx, ny, nz] (got %s %s)" % (who, vol.dtype, tuple(vol.shape)))
+    return vol.shape
+
+
+def lattice_components(vol, level, max_sweeps=None, check_every=8, jump=True):
+    """Connected components of the inside points (vol > level; a NaN is outside) of a lattice vol [nx, ny, nz] fp32 under the
+    connectivity of the mesh (the 14 neighbours along the seven edge kinds of csrc/jt_mesh.hip): labels [nx, ny, nz] int32, -1
+    outside, else the smallest flat index of the point's component -- the same bits on every run (csrc/jt_components.hip).
+
+    The host loop: `check_every` sweeps (each followed by a pointer-jumping launch when `jump`), each with a flag word of its
+    own, then ONE host read of the flags; done when a sweep lowered nothing.  After `max_sweeps` (COMPONENTS_MAX_SWEEPS) sweeps
+    without that a RuntimeError: unconverged labels are never returned."""
+    nx, ny, nz = _lattice_arg(vol, "lattice_components")
+    max_sweeps = COMPONENTS_MAX_SWEEPS if max_sweeps is None else int(max_sweeps)
+    check_every = int(check_every)
+    if max_sweeps < 1 or check_every < 1:
+        raise ValueError("lattice_components: max_sweeps and check_every are at least 1 (got %r, %r)" % (max_sweeps, check_every))
+    st = _stream()
+    labels = torch.empty(nx, ny, nz, device=vol.device, dtype=torch.int32)
+    check(lib.jt_components_init(ptr(vol), nx, ny, nz, float(level), ptr(labels), st), "jt_components_init")
+    flags = torch.empty(check_every, device=vol.device, dtype=torch.int32)
+    done = 0
+    while done < max_sweeps:
+        batch = min(check_every, max_sweeps - done)
+        flags.zero_()
+        for s in range(batch):
+            check(lib.jt_components_sweep(ptr(labels), nx, ny, nz, flags.data_ptr() + 4 * s, int(bool(jump)), st),
+                  "jt_components_sweep")
+        lowered = flags[:batch].tolist()
+        if 0 in lowered:
+            last_components_stats.update(sweeps=done + batch, converged_at=done + lowered.index(0) + 1)
+            return labels
+        done += batch
+    raise RuntimeError("lattice_components: the labels of the %d x %d x %d lattice had not converged after %d sweeps "
+                       "(max_sweeps)" % (nx, ny, nz, done))
+
+
+def component_sizes(labels):
+    """(roots [K] int64 ascending: the labels in use, counts [K] int32: their points), counted on the device from labels"""
+    nx, ny, nz = labels.shape
+    sizes = torch.zeros(labels.numel(), device=labels.device, dtype=torch.int32)
+    check(lib.jt_component_sizes(ptr(labels), nx, ny, nz, ptr(sizes), _stream()), "jt_component_sizes")
+    roots = torch.nonzero(sizes).view(-1)
+    return roots, sizes[roots]
+
+
+def keep_components(vol, level, keep_largest=None, min_points=None, fill=0.0, max_sweeps=None):
+    """vol with the components (lattice_components) that fail a test set to `fill`: (vol', kept, dropped).  keep_largest = k: the
+    k components of most points stay, ties go to the smaller label; min_points = m: components of fewer than m points go; with
+    both a component must pass both.  fill must not exceed level (a dropped point must be outside).  None, None: vol itself,
+    nothing launched, (vol, None, None)."""
+    if keep_largest is None and min_points is None:
+        return vol, None, None
+    if keep_largest is not None and (int(keep_largest) != keep_largest or keep_largest < 1):
+        raise ValueError("keep_components: keep_largest is a positive integer (got %r)" % (keep_largest,))
+    if min_points is not None and (int(min_points) != min_points or min_points < 0):
+        raise ValueError("keep_components: min_points is a non-negative integer (got %r)" % (min_points,))
+    if not float(fill) <= float(level):
+        raise ValueError("keep_components: fill = %r exceeds level = %r: a dropped point would stay inside" % (fill, level))
+    labels = lattice_components(vol, level, max_sweeps=max_sweeps)
+    roots, counts = component_sizes(labels)
+    keep = torch.ones(roots.numel(), device=vol.device, dtype=torch.bool)
+    if keep_largest is not None:
+        # roots ascend: a stable descending sort by size leaves equal sizes in the order of their labels
+        order = torch.sort(counts, descending=True, stable=True).indices
+        keep.zero_()
+        keep[order[:int(keep_largest)]] = True
+    if min_points is not None:
+        keep &= counts >= int(min_points)
+    kept = int(keep.sum())
+    table = torch.zeros(labels.numel() + 1, device=vol.device, dtype=torch.bool)      # (the last entry: label -1, outside)
+    table[roots[~keep]] = True
+    drop = table[labels.view(-1).long()].view(vol.shape)
+    return torch.where(drop, torch.full_like(vol, float(fill)), vol), kept, int(roots.numel()) - kept
+
+
+def density_gradient(cfg, density_plane, density_line, xyz, want_feat=True):
+    """(feat [n] or None, grad [n, 3]) at world points xyz [n, 3]: the density feature before shift and activation and its
+    world-space gradient (jt_density_gradient; the alpha mask is ignored, points beyond the box meet zero padding)."""
+    sd = [factor_storage(p) for p in density_plane]
+    sl = [factor_storage(p) for p in density_line]
+    fac = _factors_struct(sd, sl, None, None, None)
+    xyz = xyz.detach().contiguous().float()
+    n = xyz.shape[0]
+    feat = torch.empty(n, device=xyz.device, dtype=torch.float32) if want_feat else None
+    grad = torch.empty(n, 3, device=xyz.device, dtype=torch.float32)
+    check(lib.jt_density_gradient(cfg.scene(), fac, ptr(xyz), n, ptr(feat), ptr(grad), _stream()), "jt_density_gradient")
+    return feat, grad
+
+
+def shade_points(cfg, app_plane, app_line, basis, mlp, xyz, viewdirs):
+    """rgb [n, 3] of the appearance branch at world points xyz [n, 3] seen along viewdirs [n, 3]: every point is a ray of ONE
+    sample at z = 0 through jt_shade_forward without a workspace (the record-free k_shade_fwd<C, 0, B16>): rays_o = xyz, rays_d =
+    viewdirs, tmin = 0, no jitter, zvals = [0], shade_offset = arange(n + 1), entry_ray = arange(n), entry_smp = 0; o + d * 0
+    is o exactly.  cfg: a RenderCfg with n_samples = 1; one launch."""
+    dev = xyz.device
+    xyz = xyz.detach().contiguous().float()
+    viewdirs = viewdirs.detach().contiguous().float()
+    n = xyz.shape[0]
+    rgb = torch.empty(n, 3, device=dev, dtype=torch.float32)
+    if n == 0:
+        return rgb
+    if cfg.n_samples != 1:
+        raise ValueError("shade_points: the scene description must say n_samples = 1 (got %d)" % cfg.n_samples)
+    sap, sal = [factor_storage(p) for p in app_plane], [factor_storage(p) for p in app_line]
+    mlp_t = [t.detach().contiguous() for t in [basis] + list(mlp)]
+    fac = _factors_struct(None, None, sap, sal, None)
+    offset = torch.arange(n + 1, device=dev, dtype=torch.int32)
+    zeros_f = torch.zeros(n, device=dev, dtype=torch.float32)
+    zeros_i = torch.zeros(n, device=dev, dtype=torch.int32)
+    zvals = torch.zeros(1, device=dev, dtype=torch.float32)
+    check(lib.jt_shade_forward(cfg.scene(), fac, _mlp_struct(*mlp_t), ptr(xyz), ptr(viewdirs), None, ptr(zvals), ptr(zeros_f),
+                               ptr(offset), n, ptr(offset), ptr(zeros_i), ptr(viewdirs), ptr(rgb), n, None, 0, 0, _stream()),
+          "jt_shade_forward")
+    return rgb
+
+
 def blur_images(images, taps):
     """Separable replicate-padded blur (along W, then H) of a batch of images [n, c, H, W] with one tap vector:
     the 2-D GT blur of nerf.Model.process_GT_images (model/nerf.py:98-110) on the factor-blur kernel.  All n*c

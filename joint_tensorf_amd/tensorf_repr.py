@@ -19,7 +19,10 @@ MAT_MODE = ops.MAT_MODE
 VEC_MODE = ops.VEC_MODE
 
 # what extract_mesh returns: the arrays on the device, and the lattice they were taken on (box, points per axis, iso-level)
-Mesh = collections.namedtuple("Mesh", "vertices triangles lo hi shape level")
+# normals / colors: [nv, 3] fp32 per vertex when asked for; n_components: (kept, dropped) when a component filter ran;
+# n_degenerate_normals: vertices whose density gradient was zero or non-finite (their normal is (0, 0, 0)) when normals were formed
+Mesh = collections.namedtuple("Mesh", "vertices triangles lo hi shape level normals colors n_components n_degenerate_normals",
+                              defaults=(None, None, None, None))
 
 
 def _channel_last_param(t):
@@ -329,7 +332,69 @@ class BAT_VMSplit(torch.nn.Module):
         return vol.view(*n)
 
     @torch.no_grad()
-    def extract_mesh(self, res=None, level=0.005, cap=True, slab_points=1 << 24):
+    def point_normals(self, xyz, slab_points=1 << 22):
+        """Unit normals [n, 3] fp32 of the density field at world points xyz [n, 3], pointing out of the opaque side (the
+        orientation extract_mesh's triangles have), and the number of degenerate ones.  In order: (1) a point outside the scene
+        box on some axes (a vertex of the cap) gets the normalised sign vector over those axes; (2) otherwise -grad / |grad| of
+        the density feature (ops.density_gradient on the factors compute_alpha uses: blurred when kernel_density is set);
+        (3) where |grad| is 0 or not finite, (0, 0, 0), counted in the second result."""
+        xyz = xyz.detach().reshape(-1, 3).float()
+        dP, dL = list(self.density_plane), list(self.density_line)
+        if getattr(self, "kernel_density", None) is not None:
+            dP, dL, _, _ = ops.blur_factors(self.kernel_density, self.kernel_density, dP, dL, list(self.app_plane),
+                                            list(self.app_line))
+        cfg = self._density_cfg()
+        lo, hi = self.aabb[0].to(xyz.device), self.aabb[1].to(xyz.device)
+        out = torch.empty_like(xyz)
+        bad = torch.zeros((), device=xyz.device, dtype=torch.int64)
+        for start in range(0, xyz.shape[0], int(slab_points)):
+            p = xyz[start:start + int(slab_points)]
+            g = ops.density_gradient(cfg, dP, dL, p, want_feat=False)[1]
+            length = torch.linalg.vector_norm(g, dim=-1, keepdim=True)
+            ok = torch.isfinite(length) & (length > 0)
+            nrm = torch.where(ok, -g / torch.where(ok, length, torch.ones_like(length)), torch.zeros_like(g))
+            sign = (p > hi).float() - (p < lo).float()
+            outside = (sign != 0).any(-1, keepdim=True)
+            nrm = torch.where(outside, sign / torch.linalg.vector_norm(sign, dim=-1, keepdim=True).clamp(min=1.0), nrm)
+            bad += (~ok & ~outside).sum()
+            out[start:start + p.shape[0]] = nrm
+        return out, int(bad)
+
+    @torch.no_grad()
+    def point_colors(self, xyz, viewdirs, view_pe_progress=None, fea_pe_progress=None, slab_points=1 << 20):
+        """Colours [n, 3] fp32 in (0, 1) of the appearance branch at world points xyz [n, 3] seen along viewdirs [n, 3] (passed to
+        the MLP as they are): ops.shade_points, i.e. the forward's own record-free appearance kernel on rays of one sample, in
+        slabs.  Positions are clamped to the scene box first (a cap vertex takes the colour of the face point beneath it);
+        the appearance factors are blurred as the last forward left them (kernel_color); the PE progress values default to
+        the last forward's (1.0 without one)."""
+        xyz = xyz.detach().reshape(-1, 3).float()
+        viewdirs = viewdirs.detach().reshape(-1, 3).float()
+        if viewdirs.shape != xyz.shape:
+            raise ValueError("point_colors: one view direction per point (got %s and %s)" % (tuple(xyz.shape), tuple(viewdirs.shape)))
+        last = getattr(self, "last_render_cfg", None)
+        if view_pe_progress is None:
+            view_pe_progress = last.view_pe_progress if last is not None else 1.0
+        if fea_pe_progress is None:
+            fea_pe_progress = last.fea_pe_progress if last is not None else 1.0
+        aP, aL = list(self.app_plane), list(self.app_line)
+        g = self.gridSize.tolist()
+        plane_hw = None
+        if getattr(self, "kernel_color", None) is not None:
+            plane_hw = [(g[MAT_MODE[i][0]], g[MAT_MODE[i][1]]) for i in range(3)]      # (a blurred plane is sampled transposed: forward)
+            _, _, aP, aL = ops.blur_factors(self.kernel_color, self.kernel_color, list(self.density_plane), list(self.density_line),
+                                            aP, aL)
+        cfg = self._render_cfg(1, False, False, plane_hw, view_pe_progress, fea_pe_progress, use_mask=False)
+        lo, hi = self.aabb[0].to(xyz.device), self.aabb[1].to(xyz.device)
+        out = torch.empty_like(xyz)
+        for start in range(0, xyz.shape[0], int(slab_points)):
+            p = torch.minimum(torch.maximum(xyz[start:start + int(slab_points)], lo), hi)
+            out[start:start + p.shape[0]] = ops.shade_points(cfg, aP, aL, self.basis_mat.weight, self.renderModule.weights(), p,
+                                                             viewdirs[start:start + p.shape[0]])
+        return out
+
+    @torch.no_grad()
+    def extract_mesh(self, res=None, level=0.005, cap=True, slab_points=1 << 24, keep_largest=None, min_points=None,
+                     normals=False, colors=False, view_pe_progress=None, fea_pe_progress=None):
         """The surface {one-step opacity = level} of the field as a triangle mesh, extracted on the device (ops.mesh_from_lattice):
         a Mesh of vertices [nv, 3] fp32 in the scene box's coordinates, triangles [nt, 3] int32 with normals pointing out of the
         opaque side, and the box (lo, hi), the size (shape) and the level of the lattice the surface was taken on.  What the
@@ -338,13 +403,30 @@ class BAT_VMSplit(torch.nn.Module):
         res: None (the factor grid), an int or three -- lattice points per axis; the lattice is dense_alpha_lattice(res,
         slab_points), with the blur state the last forward left, as compute_alpha (a freshly restored checkpoint has none).
         cap: one layer of zeros round the lattice and the box grown by one lattice spacing per side, so that a surface reaching
-        the scene box is closed there.  level = 0.005 is the upstream export's."""
+        the scene box is closed there.  level = 0.005 is the upstream export's.
+        keep_largest / min_points: floaters are removed before a triangle is emitted -- ops.keep_components on the opacity
+        lattice (before the cap: its zeros join nothing) with fill = 0; Mesh.n_components = (kept, dropped).
+        normals: Mesh.normals = point_normals(vertices), Mesh.n_degenerate_normals the zero ones.  colors: Mesh.colors =
+        point_colors(vertices, -normal): the surface seen head-on ((0, 0, -1) where the normal is zero); the normals are then
+        computed whether asked for or not, and returned only if asked for."""
         vol = self.dense_alpha_lattice(res, slab_points)
         lo, hi = self.aabb[0].tolist(), self.aabb[1].tolist()
+        n_components = None
+        if keep_largest is not None or min_points is not None:
+            vol, kept, dropped = ops.keep_components(vol, level, keep_largest=keep_largest, min_points=min_points, fill=0.0)
+            n_components = (kept, dropped)
         if cap:
             vol, lo, hi = ops.cap_lattice(vol, lo, hi)
         vertices, triangles = ops.mesh_from_lattice(vol, level, lo, hi)
-        return Mesh(vertices, triangles, tuple(lo), tuple(hi), tuple(vol.shape), float(level))
+        nrm = col = n_bad = None
+        if normals or colors:
+            nrm, n_bad = self.point_normals(vertices)
+        if colors:
+            zero = (nrm == 0).all(-1, keepdim=True)
+            col = self.point_colors(vertices, torch.where(zero, nrm.new_tensor([0.0, 0.0, -1.0]), -nrm), view_pe_progress,
+                                    fea_pe_progress)
+        return Mesh(vertices, triangles, tuple(lo), tuple(hi), tuple(vol.shape), float(level), nrm if normals else None, col,
+                    n_components, n_bad if normals else None)
 
     @torch.no_grad()
     def updateAlphaMask(self, gridSize=(200, 200, 200)):
