@@ -5,6 +5,10 @@
 #pragma once
 #include "jt_common.h"
 
+#ifndef JT_SCATTER_CLAIM_DEFAULT
+#define JT_SCATTER_CLAIM_DEFAULT 1
+#endif
+
 namespace jt {
 
 // Every switch, read ONCE per process (the environment) or set through the library's setters.  DESIGN.md section 3 has the
@@ -20,6 +24,7 @@ struct Knobs {
   int scatter_waves;  // JT_SCATTER_WAVES: 8 / 12 / 16 waves per scatter workgroup, 0 = chosen by the plan
   int scatter_flags;  // JT_SCATTER_FLAGS: bit 0 line gradients through LDS, default 1
   int scatter_first;  // JT_SCATTER_FIRST: the scatter in front of the fork, default 0
+  int scatter_claim;  // JT_SCATTER_CLAIM: 0 a fixed stride per wave, 1 the twelve-wave scatter's waves draw their batches
   int wgrad_pipe;     // JT_WGRAD_PIPE: the GEMMs of chunk c forked behind the chain of chunk c, default 1
   int ablate;         // JT_ABLATE (profiling): 1 no scatter, 2 no gradient records, 4 no weight-gradient GEMMs
   int pose_bwd;       // JT_POSE_BWD: the walker-free pose-only kernels of both backwards, default 1

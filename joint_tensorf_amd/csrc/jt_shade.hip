@@ -637,6 +637,27 @@ struct ScatCfg {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
+#if JT_SCATTER_STAMP
+// profiling build only (tools/build_variant.py sstamp -DJT_SCATTER_STAMP=1; tools/stamp_scatter.py): where the waves of
+// k_shade_scatter spend their s_memtime ticks, summed over all waves and launches -- [0] set-up in front of the plane loop,
+// per plane pl [1 + 5 pl] the basis image and line reset up to the barrier, [2 + 5 pl] the batch loop, [3 + 5 pl] the wait at
+// the pass-end barrier, [4 + 5 pl] the line flush, [5 + 5 pl] the dBasis slab sum; [16] waves, [17] launches, [18] batches.
+// g_swg: per launch (a ring of kStampRing) and workgroup the constant-rate clock (100 MHz, one counter for the whole device)
+// at its start and at the end of each plane pass.
+constexpr int kStampRing = 32, kStampWgs = 256;
+__device__ unsigned long long g_sstamps[24];
+__device__ unsigned long long g_swg[kStampRing][kStampWgs][4];
+__device__ unsigned g_slaunch, g_sdone;
+#define JT_SS(k)                                                   \
+  {                                                                \
+    const unsigned long long now__ = __builtin_readcyclecounter(); \
+    ss_acc[k] += now__ - ss_last;                                  \
+    ss_last = now__;                                               \
+  }
+#else
+#define JT_SS(k)
+#endif
+
 // FLAGS bit 0 (not with DET): the line gradients of the pass's plane are summed in a workgroup-private LDS copy of the line
 // (line_floats = the longest line x channels; LDS float atomics) and added to the real gradient once per workgroup and plane --
 // a fifth of the scatter's global atomic segments.
@@ -652,15 +673,25 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // dBasis GEMM (k_wgrad<1, NTB, 0, 0, true>, 184 us alone) is gone.
 // The plane loop is OUTSIDE the batch loop (one LDS line at a time): the coordinate gradients of a sample go to g_xyz as
 // store (plane 0) / load-add-store (planes 1, 2) by the same lane.
+// `claim` (JT_SCATTER_CLAIM; the twelve-wave float shape only): the waves of a workgroup draw the workgroup's batches of a pass
+// one at a time from an LDS counter instead of taking every WAVES-th one.  A batch's time follows its flush count, and
+// consecutive batches belong to one ray, so a wave's fixed share is not an average over the scene: the waves that end early
+// wait at the pass-end barrier (profiles/scatter_pass_skew.txt).  The workgroup's SET of batches is the same either way.
+// (The workgroups of an XCD label end 8 % of the launch apart as well.  Drawing every batch from a head per label in device
+// memory removes that and costs more than it saves: 288 waves on one address, 2.13 against 1.46 ms per launch -- DESIGN.md
+// section 7.)
 template <class C, bool DET, int RUN, int WAVES, int FLAGS>
 __global__ __launch_bounds__(WAVES * 64) void k_shade_scatter(Dev D, MlpDev M, JtFactors G, const int* __restrict__ offset,
                                                               int R, float* __restrict__ g_xyz,
                                                               const float* __restrict__ rec, int chunk_start,
                                                               int chunk_cap, int cap, unsigned* __restrict__ bad,
-                                                              int line_floats, int rrows, float* __restrict__ dbslab) {
+                                                              int line_floats, int rrows, float* __restrict__ dbslab,
+                                                              int claim) {
   typedef BwdCfg<C> B;
   typedef ScatCfg<C> Q;
   constexpr bool LLINE = (FLAGS & 1) && !DET;
+  // (deterministic mode promises a fixed summation order for dBasis; the other shapes have not been measured)
+  constexpr bool CAN_CLAIM = WAVES == 12 && !DET;
   constexpr bool DB = (FLAGS & 2) != 0;
   constexpr int NS = 4 * RUN, NB = RUN / 4, NCH = Q::NCH, KS = Q::KS;
   extern __shared__ __align__(16) float smem[];
@@ -670,18 +701,43 @@ __global__ __launch_bounds__(WAVES * 64) void k_shade_scatter(Dev D, MlpDev M, J
   const int nblk = min((int)gridDim.x, (nbatch + WAVES - 1) / WAVES);  // the grid is sized for the worst case
   if ((int)blockIdx.x >= nblk) return;
   const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+#if JT_SCATTER_STAMP
+  unsigned long long ss_acc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, ss_last = __builtin_readcyclecounter(), ss_nb = 0;
+  const unsigned ss_slot = *(volatile unsigned*)&g_slaunch % kStampRing;
+  if (threadIdx.x == 0 && blockIdx.x < kStampWgs) g_swg[ss_slot][blockIdx.x][0] = wall_clock64();
+#endif
   float* sline = smem + Q::BT_FLOATS;                                    // [line cell][channel] of the pass's plane
   float* red = sline + (LLINE ? line_floats : 0);                        // (DB) [row a][channel]
   float* geo = red + (DB ? Q::RED_FLOATS : 0) + wv * Q::wave_floats(RUN, DB);
   float* gxyz = geo + NS * 4;
   float* recs = gxyz + NS * 4;
   float* gft = recs + NS * kRecWords;                                    // (DB) [32 rows][16 samples]
+  // the workgroup's batch counter of a pass: word 3 of wave 0's first geo slot, which nobody else touches (a slot holds three
+  // coordinates in four words) -- the LDS line fills the budget to within 64 bytes, and the plan's LDS size stays what it was
+  unsigned* const claim_ctr = reinterpret_cast<unsigned*>(red + (DB ? Q::RED_FLOATS : 0) + 3);
+  const bool dyn = CAN_CLAIM && claim != 0;
+  // lane 0 draws the wave's next index; draw_take hands it to the wave.  ("Increment, wrapping at 2^32 - 1" rather than "add 1",
+  // which the compiler rewrites into an add by one lane with the result broadcast AT ONCE: the wave would wait for the draw
+  // where it asks for it.)
+  auto draw_issue = [&]() -> unsigned {
+    unsigned v = 0;
+    if (lane == 0) {
+      unsigned wrap;  // (made where it is used: as a plain constant it sits in a register across the whole pass, 4 more bytes of scratch)
+      asm volatile("v_mov_b32 %0, -1" : "=v"(wrap));
+      v = __builtin_amdgcn_atomic_inc32(claim_ctr, wrap, __ATOMIC_RELAXED, "workgroup");
+    }
+    return v;
+  };
+  auto draw_take = [&](unsigned v) -> int { return (int)__builtin_amdgcn_readfirstlane(v); };
   if (DB) {  // rows past 4 KS are never written: they must read as zeros
 #pragma unroll
     for (int i = 0; i < Q::GT_FLOATS / 64; ++i) gft[lane + 64 * i] = 0.f;
   }
   const size_t RC = (size_t)rrows;
   const XcdShare xs = xcd_share(nbatch, nblk);
+  // batch of the workgroup's index i: round i / WAVES of the label's workgroups, place i % WAVES in this workgroup's row
+  const int wg_first = xs.lo + xs.rank * WAVES, wg_stride = xs.peers * WAVES;
+  JT_SS(0)
 #pragma unroll 1
   for (int pl = 0; pl < 3; ++pl) {
     // the plane's basis^T operand image [channel group][K step][lane]: lane (cl, grp) of step k holds basis[4 k + grp][ch]
@@ -692,7 +748,9 @@ __global__ __launch_bounds__(WAVES * 64) void k_shade_scatter(Dev D, MlpDev M, J
     }
     if (LLINE)
       for (int i = threadIdx.x; i < D.ll[pl] * C::CA; i += WAVES * 64) sline[i] = 0.f;
+    if (CAN_CLAIM && threadIdx.x == 0) *claim_ctr = 0u;  // (every draw of the previous pass is in front of its pass-end barrier)
     __syncthreads();
+    JT_SS(1 + 5 * pl)
     f32x4 dB[DB ? 2 : 1][NCH];
     if (DB) {
 #pragma unroll
@@ -700,7 +758,16 @@ __global__ __launch_bounds__(WAVES * 64) void k_shade_scatter(Dev D, MlpDev M, J
 #pragma unroll
         for (int c = 0; c < NCH; ++c) dB[m][c] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
-    for (int batch = xs.lo + xs.rank * WAVES + wv; batch < xs.hi; batch += xs.peers * WAVES) {
+    // static: wave wv takes the indices wv, wv + WAVES, ...; claimed: whichever index the counter hands out next, and the
+    // draw for the next batch is in flight while this one's coordinate gradients go out.  A wave stops at its first index
+    // past the share (the batch number grows with the index), so the counter ends at most WAVES past the workgroup's batches.
+    int idx = (CAN_CLAIM && dyn) ? draw_take(draw_issue()) : wv;
+    for (;;) {
+      const int batch = (CAN_CLAIM && dyn) ? wg_first + idx % WAVES + (idx / WAVES) * wg_stride : wg_first + idx;
+      if (batch >= xs.hi) break;
+#if JT_SCATTER_STAMP
+      ++ss_nb;
+#endif
       int ln = lane;
       asm volatile("" : "+v"(ln));  // (keeps per-lane address math inside the loop, see k_shade_bwd)
       const int grp = ln >> 4, cl = ln & 15;
@@ -839,6 +906,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_shade_scatter(Dev D, MlpDev M, J
       }
       wk.finish_pair(grp);
       wave_lds_sync();
+      unsigned drawn = (CAN_CLAIM && dyn) ? draw_issue() : 0u;
 #pragma unroll
       for (int ti = 0; ti < (NS + 63) / 64; ++ti) {
         const int t = ln + 64 * ti;
@@ -854,8 +922,15 @@ __global__ __launch_bounds__(WAVES * 64) void k_shade_scatter(Dev D, MlpDev M, J
         }
       }
       wave_lds_sync();
+      if (CAN_CLAIM) asm volatile("" : "+v"(drawn));  // (the value is taken HERE, not where it was asked for)
+      idx = (CAN_CLAIM && dyn) ? draw_take(drawn) : idx + wg_stride;
     }
+    JT_SS(2 + 5 * pl)
     __syncthreads();
+    JT_SS(3 + 5 * pl)
+#if JT_SCATTER_STAMP
+    if (threadIdx.x == 0 && blockIdx.x < kStampWgs) g_swg[ss_slot][blockIdx.x][1 + pl] = wall_clock64();
+#endif
     if (LLINE) {
       float* gl = G.app_line[pl];
       if (gl != nullptr)
@@ -864,6 +939,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_shade_scatter(Dev D, MlpDev M, J
           if (v != 0.f) atomicAdd(gl + i, v);
         }
     }
+    JT_SS(4 + 5 * pl)
     if (DB) {
       // the plane's dBasis slice: the waves add their accumulators into `red` one after the other (a fixed order), then the
       // workgroup's sum goes to its slab.  dB[m][c][r] is row a = 16 m + 4 grp + r, channel 16 c + cl
@@ -889,7 +965,25 @@ __global__ __launch_bounds__(WAVES * 64) void k_shade_scatter(Dev D, MlpDev M, J
       for (int i = threadIdx.x; i < Q::RED_FLOATS; i += WAVES * 64) my[i] = red[i];
     }
     __syncthreads();
+    JT_SS(5 + 5 * pl)
   }
+#if JT_SCATTER_STAMP
+  if (lane == 0) {
+    for (int k = 0; k < 16; ++k) atomicAdd(&g_sstamps[k], ss_acc[k]);
+    atomicAdd(&g_sstamps[16], 1ull);
+    atomicAdd(&g_sstamps[18], ss_nb);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {  // the last workgroup to end moves the ring on
+    __threadfence();
+    if (atomicAdd(&g_sdone, 1u) == (unsigned)nblk - 1) {
+      g_sdone = 0;
+      atomicAdd(&g_sstamps[17], 1ull);
+      __threadfence();
+      atomicAdd(&g_slaunch, 1u);
+    }
+  }
+#endif
 }
 
 // dBasis += the slabs k_shade_scatter<..., FLAGS & 2> left: [chunk][workgroup][plane][row a][channel].  The workgroups that ran
@@ -1533,6 +1627,9 @@ static Knobs read_env_knobs() {
   k.scatter_waves = env_int("JT_SCATTER_WAVES", 0);
   k.scatter_flags = env_int("JT_SCATTER_FLAGS", 1) & 1;
   k.scatter_first = env_int("JT_SCATTER_FIRST", 0) != 0;
+  // how the twelve-wave scatter's batches are split: 0 every WAVES-th batch per wave, 1 drawn from a counter per workgroup
+  k.scatter_claim = env_int("JT_SCATTER_CLAIM", JT_SCATTER_CLAIM_DEFAULT);
+  if (k.scatter_claim < 0 || k.scatter_claim > 1) k.scatter_claim = JT_SCATTER_CLAIM_DEFAULT;
   k.wgrad_pipe = env_int("JT_WGRAD_PIPE", 1) != 0;
   k.ablate = env_int("JT_ABLATE", 0);
   k.pose_bwd = env_int("JT_POSE_BWD", 1) != 0;
@@ -1575,6 +1672,19 @@ struct KindTag { typedef C Cfg; };
 template <class F>
 static auto for_kind(int kind, F&& f) { return kind == 0 ? f(KindTag<CfgBlender>()) : f(KindTag<CfgLlff>()); }
 
+#if JT_SCATTER_STAMP
+// out: g_sstamps (24 words), then g_swg (kStampRing x kStampWgs x 4 words); the counters are cleared
+extern "C" int jt_debug_read_scatter_stamps(unsigned long long* out, int n) {
+  const size_t nwg = (size_t)kStampRing * kStampWgs * 4;
+  if (n < (int)(24 + nwg)) return JT_ERR_ARG;
+  if (hipDeviceSynchronize() != hipSuccess) return JT_ERR_ARG;
+  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_sstamps), 24 * sizeof(unsigned long long)) != hipSuccess) return JT_ERR_ARG;
+  if (hipMemcpyFromSymbol(out + 24, HIP_SYMBOL(g_swg), nwg * sizeof(unsigned long long)) != hipSuccess) return JT_ERR_ARG;
+  unsigned long long z[24] = {};
+  if (hipMemcpyToSymbol(HIP_SYMBOL(g_sstamps), z, sizeof(z)) != hipSuccess) return JT_ERR_ARG;
+  return JT_OK;
+}
+#endif
 #if JT_TILE_STAMP
 extern "C" int jt_debug_read_tile_stamps(unsigned long long* out16) {
   if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_tstamps), 16 * sizeof(unsigned long long)) != hipSuccess) return JT_ERR_ARG;
@@ -2030,6 +2140,7 @@ struct ScatterArgs {
   int wgs;
   size_t lds;
   hipStream_t st;
+  int claim;
 };
 template <class C, bool DET, int RUN, int WAVES, int FLAGS>
 static void launch_scatter(const ScatterArgs& a) {
@@ -2042,7 +2153,8 @@ static void launch_scatter(const ScatterArgs& a) {
   const long nbatch = ((long)a.ccap + 4 * RUN - 1) / (4 * RUN);
   const int blocks = (int)std::min<long>((nbatch + WAVES - 1) / WAVES, (long)a.wgs);
   hipLaunchKernelGGL((k_shade_scatter<C, DET, RUN, WAVES, FLAGS>), dim3(blocks), dim3(WAVES * 64), a.lds, a.st, a.D, a.M, a.G,
-                     a.offset, a.R, a.g_xyz, a.rec, a.start, a.ccap, a.cap, a.bad, a.line_floats, a.rec_rows, a.dbasis_slabs);
+                     a.offset, a.R, a.g_xyz, a.rec, a.start, a.ccap, a.cap, a.bad, a.line_floats, a.rec_rows, a.dbasis_slabs,
+                     a.claim);
 }
 // the k_shade_scatter shapes that exist, per scene kind: a plan whose shape is not listed is JT_ERR_UNSUPPORTED
 struct ScatterShape {
@@ -2198,7 +2310,7 @@ static int launch_shade_bwd(const ShadeBwdPlan& P, const Knobs& k, const Dev& D,
       if (rc_) return rc_;
     } else {
       const ScatterArgs a = {D, M, G, offset, R, g_xyz, rc, start, ccap, cap, bad, P.line_floats, RR,
-                             dbasis_slabs + (size_t)ci * cstride, P.sc_wgs, (size_t)P.sc_lds, st};
+                             dbasis_slabs + (size_t)ci * cstride, P.sc_wgs, (size_t)P.sc_lds, st, k.scatter_claim};
       scatter->launch(a);
     }
     JT_LAUNCH_CHECK();
