@@ -40,9 +40,10 @@ extern "C" {
  * 1201: + jt_chip_geometry; 1202: + jt_shade_workspace_layout; 1203: + jt_march_forward_pose / jt_march_backward_pose; 1204: +
  * jt_lattice_indices; 1205: + jt_ssim_forward / jt_ssim_workspace_bytes; 1206: +
  * jt_image_ingest / jt_image_ingest_workspace_bytes; 1207: + jt_shade_backward_plan / jt_march_backward_plan; 1208: + jt_mesh_count / jt_mesh_emit;
- * 1209: + jt_components_init / jt_components_sweep / jt_component_sizes, jt_density_gradient, JT_COMPONENTS_TILE.  Additions bump the last two digits, anything a caller built against the old header would get wrong bumps the
+ * 1209: + jt_components_init / jt_components_sweep / jt_component_sizes, jt_density_gradient, JT_COMPONENTS_TILE; 1210: +
+ * jt_raster_project / jt_raster_draw / jt_raster_resolve, JT_RASTER_*.  Additions bump the last two digits, anything a caller built against the old header would get wrong bumps the
  * hundreds). */
-#define JT_VERSION 1209
+#define JT_VERSION 1210
 
 #define JT_OK 0
 #define JT_ERR_ARG 1         /* null pointer / bad size */
@@ -627,6 +628,54 @@ int jt_mesh_emit(const float* lattice, int nx, int ny, int nz, float level, cons
 int jt_components_init(const float* lattice, int nx, int ny, int nz, float level, int32_t* labels, void* stream);
 int jt_components_sweep(int32_t* labels, int nx, int ny, int nz, int32_t* lowered, int jump, void* stream);
 int jt_component_sizes(const int32_t* labels, int nx, int ny, int nz, int32_t* sizes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * A triangle rasteriser (csrc/jt_raster.hip): an exported mesh seen from its cameras.  Three calls, one launch each on `stream`,
+ * nothing else, no host read between them; every argument is checked before anything launches.
+ *
+ *   jt_raster_project: screen [n_views][n_vertices][4] = (x, y, 1/w, w) of vertices [n_vertices][3] under proj [n_views][12], one
+ *     3 x 4 row-major matrix per view that takes a homogeneous mesh-space point to (x w, y w, w) in pixel units.  x is the column
+ *     and y the row; the pixel of column i and row j has its centre at (i + 0.5, j + 0.5), as the ray generator has it
+ *     (camera.py:236-237), so proj = intr @ [R | t] puts a vertex where the field's rays see it.  Each of the three sums is a
+ *     chain of three fmaf from the constant term, each quotient one division.  A vertex with a non-finite coordinate, with w <
+ *     near (or a NaN w) or whose 1/w is not a positive finite number is written as (0, 0, 0, w).
+ *   jt_raster_draw: every triangle [n_triangles][3] (int32 vertex ids) of every view into zbuf [n_views][H][W] uint64, which the
+ *     caller has filled with all-ones bits.  Coverage is decided in integers: a vertex is snapped to 1/256 pixel (rintf(x *
+ *     256)), the three edge functions are evaluated at the pixel centre in int64 with the top-left fill rule -- two triangles
+ *     that share an edge cover every pixel of their union exactly once.  At a covered pixel q = (b0 q0 + b1 q1 + b2 q2) / (b0 +
+ *     b1 + b2) in fp32, b the integer edge values and q_i = 1/w_i; the nearest triangle (largest q) wins, at equal q the lower
+ *     index: ONE 64-bit atomic minimum per covered pixel on (~bits(q)) << 32 | index, so the result does not depend on the order
+ *     of execution.  status [n_views][n_triangles] uint8 says what became of every triangle, the first that applies of
+ *       JT_RASTER_DRAWN 0;
+ *       JT_RASTER_NEAR 1: a vertex with 1/w = 0 in `screen` (behind near or non-finite), or a vertex id outside [0, n_vertices):
+ *         the whole triangle is dropped, not clipped;
+ *       JT_RASTER_GUARD 2: a snapped coordinate beyond +-2^22 sub-pixels (or not a number);
+ *       JT_RASTER_EMPTY 3: zero area after snapping;
+ *       JT_RASTER_CULLED 4: cull != 0 and the screen-space winding of a back face, (x1 - x0)(y2 - y0) - (y1 - y0)(x2 - x0) > 0 --
+ *         what a triangle whose right-hand normal points away from the camera projects to under a proj with positive focal
+ *         lengths (x right, y down, z forward).
+ *     A drawn triangle need not cover a pixel.  No lane walks more than 64 pixels of a bounding box alone: larger boxes are
+ *     walked by the whole wave.
+ *   jt_raster_resolve: per pixel tri [n_views][H][W] int32 (the winner, -1 where nothing was drawn), depth fp32 (1 / q of the
+ *     key, +inf where nothing was drawn) and, with attrs [n_vertices][n_attrs] fp32 (n_attrs <= 8), out [n_views][H][W][n_attrs]:
+ *     attrs interpolated perspective-correctly, sum b_i q_i a_i / sum b_i q_i with the barycentrics recomputed from the same
+ *     integers as in draw, evaluated as a0 + l1 (a1 - a0) + l2 (a2 - a0) with l_i = b_i q_i / sum b q (a constant attribute comes
+ *     back exactly); background [n_attrs] (a HOST pointer) elsewhere.  n_attrs == 0: attrs, background and out are not read.
+ *
+ * JT_ERR_ARG for a NULL pointer, a size below 1 or a non-finite near; JT_ERR_UNSUPPORTED when n_views * H * W or n_triangles
+ * reaches 2^31, H or W exceeds 16384, n_views exceeds 65535 or n_attrs exceeds 8. */
+#define JT_RASTER_DRAWN 0
+#define JT_RASTER_NEAR 1
+#define JT_RASTER_GUARD 2
+#define JT_RASTER_EMPTY 3
+#define JT_RASTER_CULLED 4
+int jt_raster_project(const float* vertices, int n_vertices, const float* proj, int n_views, float near, float* screen,
+                      void* stream);
+int jt_raster_draw(const float* screen, int n_vertices, const int32_t* triangles, long n_triangles, int n_views, int H, int W,
+                   int cull, uint64_t* zbuf, uint8_t* status, void* stream);
+int jt_raster_resolve(const uint64_t* zbuf, const float* screen, int n_vertices, const int32_t* triangles, long n_triangles,
+                      int n_views, int H, int W, const float* attrs, int n_attrs, const float* background, int32_t* tri,
+                      float* depth, float* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -142,6 +142,9 @@ SIGNATURES = {
     "jt_components_init": (I, [P, I, I, I, F, P, P]),
     "jt_components_sweep": (I, [P, I, I, I, P, I, P]),
     "jt_component_sizes": (I, [P, I, I, I, P, P]),
+    "jt_raster_project": (I, [P, I, P, I, F, P, P]),
+    "jt_raster_draw": (I, [P, I, P, ctypes.c_long, I, I, I, I, P, P, P]),
+    "jt_raster_resolve": (I, [P, P, I, P, ctypes.c_long, I, I, I, P, I, P, P, P, P, P]),
     "jt_blur_batch_forward": (I, [P, I, P]),
     "jt_blur_batch_backward": (I, [P, I, P]),
     "jt_factor_reg_forward": (I, [P, I, I, I, P, P]),
@@ -184,7 +187,7 @@ def fused_lib():
 # the JT_VERSION of include/jt_render.h that SIGNATURES and the struct mirrors above were written against.  A constant, not a
 # read of the header at import time: a vendored copy of the package has no include/ directory beside it (tests/test_abi.py
 # holds this number, the header's and the library's together)
-JT_ABI_VERSION = 1209
+JT_ABI_VERSION = 1210
 
 
 def header_version():

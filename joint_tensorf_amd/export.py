@@ -15,6 +15,14 @@ points, stay.  `--surface.normals=true` writes per-vertex normals (the normalise
 `--surface.colors=true` per-vertex colours (the appearance branch at the vertex, seen against its normal).  Without a
 `--surface.*` option mesh.ply holds positions and triangles only.
 
+`--preview.views=N|all` looks at the result: the mesh drawn from N training cameras of cameras.json (evenly spaced over the set)
+by the device rasteriser (csrc/jt_raster.hip), OUT/preview/mesh_<idx>.png, at `--preview.size=[H,W]` (default
+data.image_size), shaded by `--preview.shade=color|normal|depth`; `--preview.cull=true` drops back faces.
+`--preview.check=true` also renders the field at the same cameras (OUT/preview/field_<idx>.png) and writes OUT/report.json:
+per view the coverage of mesh and field, their IoU, the median depth difference, the PSNR of the colours and what became of
+every triangle.  It reports; it judges nothing.  The preview needs the run's image set and a world-space scene (not
+`camera.ndc`).  Without a `--preview.*` option the export writes what it always wrote, byte for byte.
+
 Every other `--key.sub=value` is one of the dotted overrides of joint_tensorf_amd.train."""
 import sys
 
@@ -24,6 +32,11 @@ MESH_DEFAULTS = dict(res=None, level=0.005, cap=True)
 # what is done to the surface beyond extracting it: floaters removed by connected component (keep the K largest, drop those of
 # fewer than M lattice points), per-vertex normals (the density gradient) and colours (the appearance branch seen head-on)
 SURFACE_DEFAULTS = dict(keep_largest=None, min_points=None, normals=False, colors=False)
+# pictures of the mesh from the training cameras (views: how many, 0 = none, or "all"; size: [H, W], None = data.image_size;
+# shade: what a pixel shows), back faces culled or not, and the check against the volume render of the same cameras
+PREVIEW_DEFAULTS = dict(views=0, size=None, shade="color", check=False, cull=False)
+PREVIEW_SHADES = ("color", "normal", "depth")
+PREVIEW_MAX_SIZE = 16384        # what the rasteriser draws (include/jt_render.h)
 
 
 def _option_group(over, name, defaults):
@@ -47,11 +60,15 @@ def build_options(argv):
     if not isinstance(name, str):
         raise SystemExit("usage: python -m joint_tensorf_amd.export --yaml=NAME --load=CKPT --output_path=OUT [--mesh.res=N] "
                          "[--mesh.level=L] [--mesh.cap=true|false] [--surface.keep_largest=K] [--surface.min_points=M] "
-                         "[--surface.normals=true|false] [--surface.colors=true|false] [--data.root=DIR --key.sub=value ...]")
+                         "[--surface.normals=true|false] [--surface.colors=true|false] [--preview.views=N|all] [--preview.size=[H,W]] "
+                         "[--preview.shade=color|normal|depth] [--preview.check=true|false] [--preview.cull=true|false] "
+                         "[--data.root=DIR --key.sub=value ...]")
     mesh = _option_group(over, "mesh", MESH_DEFAULTS)
     surface = _option_group(over, "surface", SURFACE_DEFAULTS)
+    preview = _option_group(over, "preview", PREVIEW_DEFAULTS)
     opt = apply_overrides(load_options(name), over)
-    opt.mesh, opt.surface = mesh, surface
+    opt.mesh, opt.surface, opt.preview = mesh, surface, preview
+    _check_preview(preview)
     for k in ("keep_largest", "min_points"):
         v = surface[k]
         if v is not None:
@@ -76,6 +93,29 @@ def build_options(argv):
     return opt
 
 
+def _check_preview(preview):
+    v = preview.views
+    if v != "all":
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or float(v) != int(v) or int(v) < 0:
+            raise SystemExit("--preview.views is a non-negative integer or all (got %r)" % (v,))
+        preview.views = int(v)
+    size = preview.size
+    if size is not None:
+        size = [size] * 2 if not isinstance(size, list) else size
+        if (len(size) != 2 or any(isinstance(s, bool) or not isinstance(s, (int, float)) or float(s) != int(s)
+                                  or not 1 <= int(s) <= PREVIEW_MAX_SIZE for s in size)):
+            raise SystemExit("--preview.size is one integer or [H, W], each from 1 to %d (got %r)" % (PREVIEW_MAX_SIZE, preview.size))
+        preview.size = [int(s) for s in size]
+    if preview.shade not in PREVIEW_SHADES:
+        raise SystemExit("--preview.shade is one of %s (got %r)" % (", ".join(PREVIEW_SHADES), preview.shade))
+    for k in ("check", "cull"):
+        if not isinstance(preview[k], bool):
+            raise SystemExit("--preview.%s is true or false (got %r)" % (k, preview[k]))
+    if preview.views == 0 and any(preview[k] != PREVIEW_DEFAULTS[k] for k in PREVIEW_DEFAULTS):
+        raise SystemExit("--preview.size / shade / check / cull say how the preview is made: name its views with "
+                         "--preview.views=N or --preview.views=all")
+
+
 def has_dataset(opt):
     """whether the run names an image set (a root for the native loaders, a synthetic scene, or ready-made views)"""
     d = opt.data
@@ -89,6 +129,14 @@ def main(argv=None):
     opt = build_options(sys.argv[1:] if argv is None else list(argv))
     if not opt.get("load", None) or not opt.get("output_path", None):
         raise SystemExit("--load=CKPT and --output_path=OUT are required: the checkpoint to read, the directory to write to")
+    if opt.preview.views != 0:
+        # refused before any GPU work: the preview draws the mesh from the cameras of cameras.json
+        if not has_dataset(opt):
+            raise SystemExit("--preview.views needs the run's image set (--data.root=DIR, or --data.synthetic=true): without it no "
+                             "cameras.json is written and there is no camera to look from")
+        if opt.camera.ndc:
+            raise SystemExit("--preview.views is not available for camera.ndc scenes (space ndc): the mesh lives in the scene "
+                             "box's NDC coordinates and the projective matrix that draws it there is not built yet")
     dev = torch.device(opt.device)
     with torch.cuda.device(dev):
         m = bat_hip.Model(opt)
@@ -102,6 +150,8 @@ def main(argv=None):
         out = m.export_scene(opt, opt.output_path)
     print("joint_tensorf_amd.export: %d vertices, %d triangles in %s%s"
           % (out.n_vertices, out.n_triangles, out.mesh, "; cameras in %s" % out.cameras if out.cameras else ""), flush=True)
+    if out.get("preview", None) is not None:
+        print("joint_tensorf_amd.export: " + out.preview.summary, flush=True)
     return out
 
 

@@ -163,3 +163,27 @@ def write_cameras(path, cameras):
 def read_cameras(path):
     with open(path) as f:
         return json.load(f)
+
+
+def projection_matrices(pose, intr, size=None, image_size=None):
+    """[V, 3, 4] matrices intr @ pose that take a homogeneous mesh-space point to (x w, y w, w) in pixel units -- what
+    ops.rasterize draws through -- from world-to-camera poses [V, 3, 4] ([R | t]) and intrinsics [V, 3, 3], as the views of a
+    cameras.json hold them (tensors or arrays; the result is of the kind of `pose`).  size = (H, W) renders at another size
+    than the image_size = (H, W) the intrinsics belong to: their first row is scaled by W / W0 and their second by H / H0, as the
+    loaders rescale them when they resize an image set (datasets.py).  Pixel centres are at half-integers, as for the ray
+    generator, so a vertex lands where the field's rays see it."""
+    if len(pose.shape) != 3 or tuple(pose.shape[1:]) != (3, 4) or tuple(intr.shape) != (pose.shape[0], 3, 3):
+        raise ValueError("projection_matrices: pose is [V, 3, 4] and intr [V, 3, 3] (got %s, %s)" % (tuple(pose.shape), tuple(intr.shape)))
+    P = intr @ pose
+    if size is None:
+        return P
+    if image_size is None:
+        raise ValueError("projection_matrices: size = %r needs the image_size the intrinsics belong to" % (size,))
+    (H, W), (H0, W0) = (int(v) for v in size), (int(v) for v in image_size)
+    if min(H, W, H0, W0) < 1:
+        raise ValueError("projection_matrices: sizes are positive (got %r, %r)" % (size, image_size))
+    if (H, W) == (H0, W0):
+        return P
+    scale = [W / W0, H / H0, 1.0]
+    scale = P.new_tensor(scale) if hasattr(P, "new_tensor") else np.asarray(scale, dtype=P.dtype)
+    return scale[None, :, None] * P

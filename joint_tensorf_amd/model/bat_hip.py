@@ -1116,6 +1116,141 @@ class Model(torch.nn.Module):
                    "views": [{"idx": i, "pose": plain(pose[i]), "intr": plain(intr[i]), "pose_aligned": plain(aligned[i])}
                              for i in range(pose.shape[0])]}
         out.cameras = mesh_io.write_cameras(os.path.join(directory, "cameras.json"), cameras)
+        if (opt.get("preview", None) or {}).get("views", 0):
+            out.preview = self.preview_scene(opt, directory, mesh=mesh)
+        return out
+
+    # ---- a look at the exported mesh from the cameras it was exported with --------------------------------------
+    PREVIEW_REPORT_KEYS = ("coverage_mesh", "coverage_field", "iou", "depth_abs_median", "psnr_color")
+
+    @torch.no_grad()
+    def preview_scene(self, opt, directory, mesh=None):
+        """<directory>/preview/mesh_<idx>.png: the mesh (extract_mesh's result; extracted from opt.mesh / opt.surface when not
+        given) drawn by the device rasteriser (ops.rasterize) from opt.preview.views training cameras, evenly spaced over the set
+        ("all": every one), at opt.preview.size = [H, W] (default the image set's size; the intrinsics are rescaled), shaded by
+        opt.preview.shade: `color` (the vertex colours; point_colors against the normal when the mesh carries none), `normal`
+        (0.5 n + 0.5) or `depth` (inverse depth through eval_io.normalized_invdepth); opt.preview.cull drops back faces.
+
+        With opt.preview.check also preview/field_<idx>.png, the field rendered at the same cameras and size (render_by_slices,
+        eval mode), and <directory>/report.json: per view coverage_mesh (share of pixels a triangle covers), coverage_field
+        (opacity >= 0.5), their iou, depth_abs_median (over pixels the mesh covers and the field renders with opacity >= 0.99;
+        the field's depth with the `- near + 0.05` of batBase.py:150 undone; both are distances along the camera axis),
+        psnr_color (shade color: over pixels both cover) and the five triangle counts (ops.RASTER_STATUS); then the means over
+        the views.  A value over an empty set of pixels is null and left out of its mean.  Nothing is judged: the tool reports.
+
+        Returns Opt(directory, views: the indices drawn, report: the path or None, means: the dict or None, summary: one line)."""
+        import json
+        from .. import eval_io, mesh_io
+        cfg = opt.preview
+        if opt.camera.ndc:
+            raise ValueError("preview_scene: camera.ndc scenes (space ndc) are not drawn: the mesh lives in the scene box's NDC "
+                             "coordinates and the projective matrix for it is not built yet")
+        if self.train_data is None:
+            raise ValueError("preview_scene: no training set is loaded, so there is no camera to look from")
+        nerf = self.graph.nerf
+        tf = nerf.tensorf
+        if mesh is None:
+            mcfg, scfg = opt.get("mesh", None) or {}, opt.get("surface", None) or {}
+            mesh = tf.extract_mesh(res=mcfg.get("res", None), level=float(mcfg.get("level", 0.005)), cap=bool(mcfg.get("cap", True)),
+                                   keep_largest=scfg.get("keep_largest", None), min_points=scfg.get("min_points", None))
+        shade = cfg.get("shade", "color")
+        if shade not in ("color", "normal", "depth"):
+            raise ValueError("preview_scene: shade is color, normal or depth (got %r)" % (shade,))
+        if mesh.triangles.shape[0] == 0:
+            raise ValueError("preview_scene: the mesh is empty (level %r): nothing to draw" % (mesh.level,))
+        pose, _ = self.get_all_training_poses(opt)
+        n = int(pose.shape[0])
+        k = n if cfg.views == "all" else min(int(cfg.views), n)
+        idx = sorted(set(int(round(i * (n - 1) / max(k - 1, 1))) for i in range(k)))
+        H, W = (int(v) for v in (cfg.get("size", None) or (opt.H, opt.W)))
+        pose = pose[idx].contiguous()
+        intr = self.train_data.all.intr[idx].to(pose.device, torch.float32)
+        proj = mesh_io.projection_matrices(pose, intr, size=(H, W), image_size=(opt.H, opt.W))
+        white = bool(opt.nerf.setbg_opaque)
+        attrs, background = None, 0.0
+        if shade in ("color", "normal"):
+            nrm = mesh.normals if mesh.normals is not None else tf.point_normals(mesh.vertices)[0]
+            if shade == "normal":
+                attrs = 0.5 * nrm + 0.5
+            elif mesh.colors is not None:
+                attrs, background = mesh.colors, 1.0 if white else 0.0
+            else:
+                pe = {}
+                if getattr(nerf, "progress_host", None) is not None:
+                    for key, name in (("view_pe_progress", "c2f_view_pe_schedule"), ("fea_pe_progress", "c2f_fea_pe_schedule")):
+                        pe[key] = interp_schedule(nerf.progress_host, opt[name]) if _has(opt, name) else 1.0
+                zero = (nrm == 0).all(-1, keepdim=True)
+                attrs = tf.point_colors(mesh.vertices, torch.where(zero, nrm.new_tensor([0.0, 0.0, -1.0]), -nrm), **pe)
+                background = 1.0 if white else 0.0
+        drawn = ops.rasterize(mesh.vertices, mesh.triangles, proj, H, W, attrs=attrs, cull=bool(cfg.get("cull", False)),
+                              background=background)
+        covered = drawn.tri >= 0
+        invdepth = torch.where(covered, 1 / drawn.depth, torch.zeros_like(drawn.depth))
+        path = os.path.join(directory, "preview")
+        os.makedirs(path, exist_ok=True)
+        for j, i in enumerate(idx):
+            picture = (eval_io.normalized_invdepth(opt, invdepth[j][None]) if shade == "depth" else drawn.attrs[j].permute(2, 0, 1))
+            eval_io.save_png(picture, os.path.join(path, "mesh_%d.png" % i))
+        out = Opt(directory=path, views=idx, report=None, means=None,
+                  summary="preview of %d views at %d x %d in %s" % (len(idx), H, W, path))
+        if not cfg.get("check", False):
+            return out
+        # the field at the same cameras and size: the render reads the size from opt.H / opt.W
+        self.graph.eval()
+        intr_s = intr.clone()
+        intr_s[:, 0] *= W / opt.W
+        intr_s[:, 1] *= H / opt.H
+        intr_inv = torch.linalg.inv(intr_s)
+        size0 = (opt.H, opt.W)
+        rows = []
+        counts = drawn.status_counts.tolist()
+        try:
+            opt.H, opt.W = H, W
+            for j, i in enumerate(idx):
+                ret = self.graph.render_by_slices(opt, pose[j:j + 1], intr_inv=intr_inv[j:j + 1], intr=intr_s[j:j + 1])
+                opacity = ret.opacity.view(H, W)
+                rgb = ret.rgb.view(H, W, 3)
+                depth_f = ret.depth.view(H, W) + float(tf.near_far[0]) - 0.05      # (the near plane this render marched from)
+                if shade == "depth":
+                    picture = eval_io.normalized_invdepth(opt, (1 / (ret.depth.view(H, W) / opacity + 1e-10))[None])
+                else:
+                    picture = rgb.permute(2, 0, 1)
+                eval_io.save_png(picture, os.path.join(path, "field_%d.png" % i))
+                m, f = covered[j], opacity >= 0.5
+                union = (m | f).sum()
+                solid = m & (opacity >= 0.99)
+                both = m & f
+                row = {"idx": i, "coverage_mesh": float(m.float().mean()), "coverage_field": float(f.float().mean()),
+                       "iou": float((m & f).sum() / union) if int(union) else 1.0,
+                       "depth_abs_median": float((drawn.depth[j] - depth_f)[solid].abs().median()) if int(solid.sum()) else None,
+                       "psnr_color": None}
+                if shade == "color" and int(both.sum()):
+                    mse = ((drawn.attrs[j] - rgb)[both] ** 2).mean().clamp(min=1e-10)
+                    row["psnr_color"] = float(-10 * torch.log10(mse))
+                row["triangles"] = dict(zip(ops.RASTER_STATUS, (int(c) for c in counts[j])))
+                rows.append(row)
+        finally:
+            opt.H, opt.W = size0
+        means = {}
+        for key in self.PREVIEW_REPORT_KEYS:
+            vals = [r[key] for r in rows if r[key] is not None]
+            means[key] = sum(vals) / len(vals) if vals else None
+        means["triangles"] = {s: sum(r["triangles"][s] for r in rows) / len(rows) for s in ops.RASTER_STATUS}
+        report = {"mesh": "mesh.ply", "cameras": "cameras.json", "size": [H, W], "shade": shade, "cull": bool(cfg.get("cull", False)),
+                  "n_triangles": int(mesh.triangles.shape[0]), "views": rows, "mean": means}
+        out.report = os.path.join(directory, "report.json")
+        with open(out.report, "w") as fh:
+            json.dump(report, fh, indent=1)
+            fh.write("\n")
+        out.means = means
+
+        def show(v, fmt):
+            return "n/a" if v is None else fmt % v
+        out.summary = ("preview of %d views at %d x %d: mesh covers %s, field %s, IoU %s, median depth difference %s, colour PSNR %s; "
+                       "%d of %d triangles drawn per view; report in %s"
+                       % (len(idx), H, W, show(means["coverage_mesh"], "%.3f"), show(means["coverage_field"], "%.3f"),
+                          show(means["iou"], "%.3f"), show(means["depth_abs_median"], "%.4f"), show(means["psnr_color"], "%.2f dB"),
+                          round(means["triangles"]["drawn"]), mesh.triangles.shape[0], out.report))
         return out
 
     # ---- evaluation (SURVEY 8(f) N1) ---------------------------------------------------------------------------

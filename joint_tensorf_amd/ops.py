@@ -1663,6 +1663,96 @@ def keep_components(vol, level, keep_largest=None, min_points=None, fill=0.0, ma
     return torch.where(drop, torch.full_like(vol, float(fill)), vol), kept, int(roots.numel()) - kept
 
 
+# what jt_raster_draw's status bytes say (include/jt_render.h: JT_RASTER_*), in the order of rasterize's status_counts columns
+RASTER_STATUS = ("drawn", "near", "guard", "empty", "culled")
+RASTER_MAX_ATTRS = 8
+
+
+def raster_project(vertices, proj, near=1e-3):
+    """jt_raster_project: screen [V, nv, 4] = (x, y, 1/w, w) of vertices [nv, 3] under proj [V, 3, 4]; one launch"""
+    V, nv = proj.shape[0], vertices.shape[0]
+    screen = torch.empty(V, nv, 4, device=vertices.device, dtype=torch.float32)
+    check(lib.jt_raster_project(ptr(vertices), nv, ptr(proj), V, float(near), ptr(screen), _stream()), "jt_raster_project")
+    return screen
+
+
+def raster_draw(screen, triangles, H, W, cull=False):
+    """jt_raster_draw into a fresh z-buffer: (zbuf [V, H, W] int64 holding the uint64 keys, all-ones bits where nothing was drawn;
+    status [V, nt] uint8); a fill and one launch"""
+    V, nv, nt = screen.shape[0], screen.shape[1], triangles.shape[0]
+    zbuf = torch.full((V, H, W), -1, device=screen.device, dtype=torch.int64)
+    status = torch.empty(V, nt, device=screen.device, dtype=torch.uint8)
+    check(lib.jt_raster_draw(ptr(screen), nv, ptr(triangles), nt, V, H, W, int(bool(cull)), ptr(zbuf), ptr(status), _stream()),
+          "jt_raster_draw")
+    return zbuf, status
+
+
+def raster_resolve(zbuf, screen, triangles, attrs=None, background=0.0):
+    """jt_raster_resolve: (tri [V, H, W] int32, depth [V, H, W] fp32, out [V, H, W, C] fp32 or None without attrs); one launch"""
+    V, H, W = zbuf.shape
+    nv, nt = screen.shape[1], triangles.shape[0]
+    dev = zbuf.device
+    tri = torch.empty(V, H, W, device=dev, dtype=torch.int32)
+    depth = torch.empty(V, H, W, device=dev, dtype=torch.float32)
+    C = 0 if attrs is None else attrs.shape[1]
+    out = torch.empty(V, H, W, C, device=dev, dtype=torch.float32) if C else None
+    bg = None
+    if C:
+        bg = [float(background)] * C if not hasattr(background, "__len__") else [float(v) for v in background]
+        if len(bg) != C:
+            raise ValueError("rasterize: %d background values for %d attributes" % (len(bg), C))
+        bg = (ctypes.c_float * C)(*bg)
+    check(lib.jt_raster_resolve(ptr(zbuf), ptr(screen), nv, ptr(triangles), nt, V, H, W, ptr(attrs), C, bg, ptr(tri), ptr(depth),
+                                ptr(out), _stream()), "jt_raster_resolve")
+    return tri, depth, out
+
+
+def rasterize(vertices, triangles, proj, H, W, attrs=None, near=1e-3, cull=False, background=0.0, views_per_call=8):
+    """A triangle mesh (vertices [nv, 3] fp32, triangles [nt, 3] int32) seen through proj [V, 3, 4] -- one matrix per view that
+    takes a homogeneous mesh-space point to (x w, y w, w) in pixel units, pixel centres at half-integers (mesh_io.
+    projection_matrices builds it from cameras) -- at H x W (csrc/jt_raster.hip).  Returns Opt(tri [V, H, W] int32: the nearest
+    triangle, -1 where none; depth [V, H, W] fp32: its w, +inf where none; attrs [V, H, W, C]: `attrs` [nv, C <= 8] interpolated
+    perspective-correctly, `background` (a number or C numbers) where nothing was drawn, None without attrs; status_counts [V, 5]
+    int64: triangles drawn / dropped behind `near` or non-finite / beyond the guard band / of zero area / culled as back faces).
+
+    Per slab of `views_per_call` views: a z-buffer of 8 bytes per pixel is allocated and cleared, then jt_raster_project,
+    jt_raster_draw, jt_raster_resolve.  Everything stays on the device and nothing is read back; coverage is decided in
+    integers and depth by one 64-bit atomic minimum per pixel, so two calls return the same bits however the views are batched."""
+    from .options import Opt
+    H, W, step = int(H), int(W), int(views_per_call)
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or triangles.dim() != 2 or triangles.shape[1] != 3:
+        raise ValueError("rasterize: vertices are [nv, 3] and triangles [nt, 3] (got %s, %s)" % (tuple(vertices.shape), tuple(triangles.shape)))
+    if triangles.dtype != torch.int32:
+        raise ValueError("rasterize: triangles are int32 vertex ids (got %s)" % triangles.dtype)
+    if proj.dim() != 3 or tuple(proj.shape[1:]) != (3, 4) or proj.shape[0] < 1:
+        raise ValueError("rasterize: proj is [V, 3, 4] with V >= 1 (got %s)" % (tuple(proj.shape),))
+    if vertices.shape[0] < 1 or triangles.shape[0] < 1:
+        raise ValueError("rasterize: an empty mesh (%d vertices, %d triangles)" % (vertices.shape[0], triangles.shape[0]))
+    if H < 1 or W < 1 or step < 1:
+        raise ValueError("rasterize: H, W and views_per_call are at least 1 (got %d, %d, %d)" % (H, W, step))
+    dev = vertices.device
+    vertices = vertices.detach().contiguous().float()
+    triangles = triangles.detach().contiguous()
+    proj = proj.detach().to(dev).contiguous().float()
+    if attrs is not None:
+        attrs = attrs.detach().contiguous().float()
+        if attrs.dim() != 2 or attrs.shape[0] != vertices.shape[0] or not 1 <= attrs.shape[1] <= RASTER_MAX_ATTRS:
+            raise ValueError("rasterize: attrs are [nv, C] with 1 <= C <= %d (got %s for %d vertices)"
+                             % (RASTER_MAX_ATTRS, tuple(attrs.shape), vertices.shape[0]))
+    codes = torch.arange(len(RASTER_STATUS), device=dev, dtype=torch.uint8)
+    tri, depth, out, counts = [], [], [], []
+    for v0 in range(0, proj.shape[0], step):
+        screen = raster_project(vertices, proj[v0:v0 + step], near)
+        zbuf, status = raster_draw(screen, triangles, H, W, cull)
+        t, d, o = raster_resolve(zbuf, screen, triangles, attrs, background)
+        tri.append(t)
+        depth.append(d)
+        out.append(o)
+        counts.append(torch.stack([(status == c).sum(1) for c in codes], 1))
+    return Opt(tri=torch.cat(tri), depth=torch.cat(depth), attrs=torch.cat(out) if attrs is not None else None,
+               status_counts=torch.cat(counts))
+
+
 def density_gradient(cfg, density_plane, density_line, xyz, want_feat=True):
     """(feat [n] or None, grad [n, 3]) at world points xyz [n, 3]: the density feature before shift and activation and its
     world-space gradient (jt_density_gradient; the alpha mask is ignored, points beyond the box meet zero padding)."""
