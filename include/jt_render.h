@@ -41,9 +41,10 @@ extern "C" {
  * jt_lattice_indices; 1205: + jt_ssim_forward / jt_ssim_workspace_bytes; 1206: +
  * jt_image_ingest / jt_image_ingest_workspace_bytes; 1207: + jt_shade_backward_plan / jt_march_backward_plan; 1208: + jt_mesh_count / jt_mesh_emit;
  * 1209: + jt_components_init / jt_components_sweep / jt_component_sizes, jt_density_gradient, JT_COMPONENTS_TILE; 1210: +
- * jt_raster_project / jt_raster_draw / jt_raster_resolve, JT_RASTER_*.  Additions bump the last two digits, anything a caller built against the old header would get wrong bumps the
+ * jt_raster_project / jt_raster_draw / jt_raster_resolve, JT_RASTER_*; 1211: + jt_mesh_unwarp_ndc / jt_mesh_filter_count / jt_mesh_filter_emit,
+ * JT_UNWARP_*.  Additions bump the last two digits, anything a caller built against the old header would get wrong bumps the
  * hundreds). */
-#define JT_VERSION 1210
+#define JT_VERSION 1211
 
 #define JT_OK 0
 #define JT_ERR_ARG 1         /* null pointer / bad size */
@@ -607,6 +608,48 @@ int jt_mesh_count(const float* lattice, int nx, int ny, int nz, float level, uin
 int jt_mesh_emit(const float* lattice, int nx, int ny, int nz, float level, const float* lo3, const float* hi3,
                  const uint8_t* edge_flags, const int64_t* vert_offset, const int64_t* tri_offset, long n_vertices,
                  long n_triangles, float* vertices, int32_t* triangles, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * NDC meshes in world space (csrc/jt_mesh.hip).  A `camera.ndc` scene lives in the NDC coordinates of the ray generator
+ * (camera.py:303-340; the centre shift moves ray origins only and does not enter): with n = ndc_near, sx = fx / cx, sy = fy / cy
+ *     xn = sx x / z,   yn = sy y / z,   zn = 1 - 2 n / z            (world, camera-like frame, z forward -> NDC)
+ *     u = 1 - zn,   z = 2 n / u,   x = xn z / sx,   y = yn z / sy   (NDC -> world), defined for u > 0:
+ * zn = 1 is infinity and zn > 1 lies behind it.  The map is projective (planes go to planes) with det J = 2 n sx sy / z^4 > 0, so
+ * the winding of a triangle is preserved.  A normal is a gradient direction and transforms by J^T; scaled by the positive z,
+ *     n_world ~ (sx nx, sy ny, (1 - zn) nz - xn nx - yn ny), then normalised; (0, 0, 0) stays (0, 0, 0).
+ *
+ *   jt_mesh_unwarp_ndc: one launch, one lane per vertex of vertices [n][3] (NDC) and, when not NULL, normals [n][3] -> world
+ *     [n][3], world_normals [n][3] (not touched without normals) and status [n] uint8, the first that applies of
+ *       JT_UNWARP_BEYOND 1: a non-finite input coordinate, u <= 0, or a non-finite result;
+ *       JT_UNWARP_FAR 2: max_depth > 0 and z > max_depth (z == max_depth is kept; max_depth <= 0: no limit);
+ *       JT_UNWARP_KEPT 0.
+ *     A vertex that is not kept is written as zeros, position and normal.  Every component is a chain of correctly rounded fp32
+ *     operations on the one u = 1 - zn: z = (2 n) / u, x = (xn z) / sx, y = (yn z) / sy -- at most four roundings each, whatever
+ *     the compiler contracts; the normal's third component is fma(u, nz, -fma(xn, nx, yn ny)), its length one fma chain and a
+ *     square root, each component one division; a length that is zero or not finite gives (0, 0, 0).
+ *   jt_mesh_filter_count: per triangle of triangles [n_triangles][3] keep[t] = 1 iff its three ids lie in [0, n_vertices) and
+ *     their statuses are 0, and cause[t] = 0 for a kept one, else the first that applies of 1 (an id out of range, a vertex
+ *     beyond) and 2 (a vertex far); used[v] = 1 for every vertex of a kept triangle (used [n_vertices], zeroed by the caller;
+ *     several lanes may store the same 1; no atomics).
+ *   the caller scans keep and used exclusively into int64 (tri_offset[t], vert_offset[v]) and reads the two totals;
+ *   jt_mesh_filter_emit: kept triangle t becomes row tri_offset[t] of triangles_out with ids vert_offset[id]; used vertex v becomes
+ *     row vert_offset[v] of vertices_out and, for normals / colors [n_vertices][3] fp32 that are not NULL, of normals_out /
+ *     colors_out.  Both keep their original order; two runs give the same bits.  Stores past n_vertices_out / n_triangles_out are
+ *     dropped; n_vertices_out == 0 launches nothing.
+ * One launch each on `stream`, nothing else.  JT_ERR_ARG for a NULL pointer, a count below 1, an out count above its in count, a
+ * NaN max_depth or an sx, sy or ndc_near that is not a positive finite number; JT_ERR_UNSUPPORTED when n (n_vertices) or 3
+ * n_triangles reaches 2^31. */
+#define JT_UNWARP_KEPT 0
+#define JT_UNWARP_BEYOND 1
+#define JT_UNWARP_FAR 2
+int jt_mesh_unwarp_ndc(const float* vertices, const float* normals, long n, float sx, float sy, float ndc_near, float max_depth,
+                       float* world, float* world_normals, uint8_t* status, void* stream);
+int jt_mesh_filter_count(const int32_t* triangles, long n_triangles, const uint8_t* status, long n_vertices, uint8_t* keep,
+                         uint8_t* cause, uint8_t* used, void* stream);
+int jt_mesh_filter_emit(const float* vertices, const float* normals, const float* colors, long n_vertices,
+                        const int32_t* triangles, long n_triangles, const uint8_t* keep, const uint8_t* used,
+                        const int64_t* vert_offset, const int64_t* tri_offset, long n_vertices_out, long n_triangles_out,
+                        float* vertices_out, float* normals_out, float* colors_out, int32_t* triangles_out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Connected components of a lattice's inside points (csrc/jt_components.hip), with the connectivity of the mesh above: two

@@ -11,6 +11,10 @@
 //
 // Lattice [nx][ny][nz] fp32, z fastest; a point is inside iff v > level (a NaN is outside).  One thread per point, consecutive
 // threads along z; a corner is addressed by its offset mask m = dx | dy << 1 | dz << 2.
+//
+// Below the extraction: the mesh of a forward-facing (camera.ndc) scene carried from the scene box's NDC coordinates to world
+// space, one lane per vertex (k_mesh_unwarp_ndc), and the triangles that lost a vertex on the way removed in the same count /
+// scan / emit form (k_mesh_filter_count, k_mesh_filter_emit).  256 threads, 64-bit indexing, no LDS, no atomics.
 #include "jt_common.h"
 
 namespace jt {
@@ -227,6 +231,106 @@ static int mesh_shape(const float* lattice, int nx, int ny, int nz, float level,
   return *n > (1l << 27) ? JT_ERR_UNSUPPORTED : JT_OK;
 }
 
+// ---- a mesh of an NDC scene carried to world space (include/jt_render.h: "NDC meshes in world space") ----------------------
+// The ray generator's NDC (jt_camera.hip) is xn = sx x/z, yn = sy y/z, zn = 1 - 2n/z; its inverse with u = 1 - zn is z = 2n/u,
+// x = xn z/sx, y = yn z/sy, defined for u > 0.  One lane per vertex; every operation is rounded on its own (__f*_rn, fmaf), so the
+// bits do not depend on contraction: u one rounding (none for zn in [0.5, 2], Sterbenz), z two, x and y four.  A normal is a
+// gradient direction and goes through J^T, scaled by the positive z: (sx nx, sy ny, u nz - xn nx - yn ny), then normalised.
+constexpr uint8_t kUnwarpKept = 0, kUnwarpBeyond = 1, kUnwarpFar = 2;
+
+__global__ __launch_bounds__(kMeshThreads) void k_mesh_unwarp_ndc(const float* __restrict__ vertices, const float* __restrict__ normals,
+                                                                  long n, float sx, float sy, float two_near, float max_depth,
+                                                                  float* __restrict__ world, float* __restrict__ world_normals,
+                                                                  uint8_t* __restrict__ status) {
+  const long i = (long)blockIdx.x * kMeshThreads + threadIdx.x;
+  if (i >= n) return;
+  const float xn = vertices[3 * i], yn = vertices[3 * i + 1], zn = vertices[3 * i + 2];
+  const float u = __fsub_rn(1.f, zn);
+  const float z = __fdiv_rn(two_near, u);
+  const float x = __fdiv_rn(__fmul_rn(xn, z), sx);
+  const float y = __fdiv_rn(__fmul_rn(yn, z), sy);
+  const bool finite_in = __builtin_isfinite(xn) && __builtin_isfinite(yn) && __builtin_isfinite(zn);
+  const bool finite_out = __builtin_isfinite(x) && __builtin_isfinite(y) && __builtin_isfinite(z);
+  uint8_t st = kUnwarpKept;
+  if (!finite_in || !(u > 0.f) || !finite_out) st = kUnwarpBeyond;
+  else if (max_depth > 0.f && z > max_depth) st = kUnwarpFar;
+  const bool kept = st == kUnwarpKept;
+  world[3 * i] = kept ? x : 0.f;
+  world[3 * i + 1] = kept ? y : 0.f;
+  world[3 * i + 2] = kept ? z : 0.f;
+  status[i] = st;
+  if (normals) {
+    const float nx = normals[3 * i], ny = normals[3 * i + 1], nz = normals[3 * i + 2];
+    const float a = __fmul_rn(sx, nx), b = __fmul_rn(sy, ny);
+    const float c = fmaf(u, nz, -fmaf(xn, nx, __fmul_rn(yn, ny)));
+    const float len = __fsqrt_rn(fmaf(a, a, fmaf(b, b, __fmul_rn(c, c))));
+    const bool ok = kept && len > 0.f && __builtin_isfinite(len);      // (false for a NaN; a zero normal stays zero)
+    world_normals[3 * i] = ok ? __fdiv_rn(a, len) : 0.f;
+    world_normals[3 * i + 1] = ok ? __fdiv_rn(b, len) : 0.f;
+    world_normals[3 * i + 2] = ok ? __fdiv_rn(c, len) : 0.f;
+  }
+}
+
+// The triangles whose three vertices were all kept, in count / scan / emit form like the extraction above.  k_mesh_filter_count:
+// keep[t] = 1 iff the three ids are in range and their statuses 0; cause[t] = 0 kept, else the first that applies of 1 (an id out
+// of range or a vertex beyond) and 2 (a vertex too far); used[v] = 1 for every vertex of a kept triangle (zeroed by the caller;
+// lanes that store the same 1 do not race for a value).  The caller scans keep and used; k_mesh_filter_emit writes kept triangle
+// t as row tri_offset[t] with ids vert_offset[id], and used vertex v (position, normal, colour) as row vert_offset[v]: the order
+// of both is the original one and two runs give the same bits.
+__global__ __launch_bounds__(kMeshThreads) void k_mesh_filter_count(const int32_t* __restrict__ triangles, long nt,
+                                                                    const uint8_t* __restrict__ status, long nv,
+                                                                    uint8_t* __restrict__ keep, uint8_t* __restrict__ cause,
+                                                                    uint8_t* __restrict__ used) {
+  const long t = (long)blockIdx.x * kMeshThreads + threadIdx.x;
+  if (t >= nt) return;
+  const long id[3] = {triangles[3 * t], triangles[3 * t + 1], triangles[3 * t + 2]};
+  bool beyond = false, far = false;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const bool in_range = id[c] >= 0 && id[c] < nv;
+    const uint8_t s = in_range ? status[id[c]] : kUnwarpBeyond;
+    beyond |= s == kUnwarpBeyond || s > kUnwarpFar;
+    far |= s == kUnwarpFar;
+  }
+  const bool k = !beyond && !far;
+  keep[t] = k ? 1 : 0;
+  cause[t] = k ? kUnwarpKept : beyond ? kUnwarpBeyond : kUnwarpFar;
+  if (k) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) used[id[c]] = 1;
+  }
+}
+
+__global__ __launch_bounds__(kMeshThreads) void k_mesh_filter_emit(
+    const float* __restrict__ vertices, const float* __restrict__ normals, const float* __restrict__ colors, long nv,
+    const int32_t* __restrict__ triangles, long nt, const uint8_t* __restrict__ keep, const uint8_t* __restrict__ used,
+    const int64_t* __restrict__ vert_offset, const int64_t* __restrict__ tri_offset, long nv_out, long nt_out,
+    float* __restrict__ vertices_out, float* __restrict__ normals_out, float* __restrict__ colors_out,
+    int32_t* __restrict__ triangles_out) {
+  const long i = (long)blockIdx.x * kMeshThreads + threadIdx.x;
+  if (i < nt && keep[i]) {
+    const long at = tri_offset[i];
+    if ((unsigned long)at < (unsigned long)nt_out) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const long id = triangles[3 * i + c];       // (in range: keep[i] says so)
+        triangles_out[3 * at + c] = (id >= 0 && id < nv) ? (int32_t)vert_offset[id] : 0;
+      }
+    }
+  }
+  if (i < nv && used[i]) {
+    const long at = vert_offset[i];
+    if ((unsigned long)at < (unsigned long)nv_out) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        vertices_out[3 * at + c] = vertices[3 * i + c];
+        if (normals) normals_out[3 * at + c] = normals[3 * i + c];
+        if (colors) colors_out[3 * at + c] = colors[3 * i + c];
+      }
+    }
+  }
+}
+
 }  // namespace jt
 
 using namespace jt;
@@ -259,6 +363,54 @@ extern "C" int jt_mesh_emit(const float* lattice, int nx, int ny, int nz, float 
   hipLaunchKernelGGL(k_mesh_emit, dim3((unsigned)((n + kMeshThreads - 1) / kMeshThreads)), dim3(kMeshThreads), 0,
                      (hipStream_t)stream, lattice, nx, ny, nz, level, box, edge_flags, vert_offset, tri_offset, n_vertices,
                      n_triangles, vertices, triangles);
+  JT_LAUNCH_CHECK();
+  return JT_OK;
+}
+
+extern "C" int jt_mesh_unwarp_ndc(const float* vertices, const float* normals, long n, float sx, float sy, float ndc_near,
+                                  float max_depth, float* world, float* world_normals, uint8_t* status, void* stream) {
+  if (!vertices || !world || !status || (normals && !world_normals) || n < 1) return JT_ERR_ARG;
+  if (!(sx > 0.f) || !(sy > 0.f) || !(ndc_near > 0.f) || !__builtin_isfinite(sx) || !__builtin_isfinite(sy) ||
+      !__builtin_isfinite(ndc_near) || max_depth != max_depth)
+    return JT_ERR_ARG;
+  if (n >= (1l << 31)) return JT_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(k_mesh_unwarp_ndc, dim3((unsigned)((n + kMeshThreads - 1) / kMeshThreads)), dim3(kMeshThreads), 0,
+                     (hipStream_t)stream, vertices, normals, n, sx, sy, 2.f * ndc_near, max_depth, world, world_normals, status);
+  JT_LAUNCH_CHECK();
+  return JT_OK;
+}
+
+static int mesh_filter_shape(long n_vertices, long n_triangles) {
+  if (n_vertices < 1 || n_triangles < 1) return JT_ERR_ARG;
+  return (n_vertices >= (1l << 31) || 3 * n_triangles >= (1l << 31)) ? JT_ERR_UNSUPPORTED : JT_OK;
+}
+
+extern "C" int jt_mesh_filter_count(const int32_t* triangles, long n_triangles, const uint8_t* status, long n_vertices,
+                                    uint8_t* keep, uint8_t* cause, uint8_t* used, void* stream) {
+  if (!triangles || !status || !keep || !cause || !used) return JT_ERR_ARG;
+  if (const int rc = mesh_filter_shape(n_vertices, n_triangles)) return rc;
+  hipLaunchKernelGGL(k_mesh_filter_count, dim3((unsigned)((n_triangles + kMeshThreads - 1) / kMeshThreads)), dim3(kMeshThreads), 0,
+                     (hipStream_t)stream, triangles, n_triangles, status, n_vertices, keep, cause, used);
+  JT_LAUNCH_CHECK();
+  return JT_OK;
+}
+
+extern "C" int jt_mesh_filter_emit(const float* vertices, const float* normals, const float* colors, long n_vertices,
+                                   const int32_t* triangles, long n_triangles, const uint8_t* keep, const uint8_t* used,
+                                   const int64_t* vert_offset, const int64_t* tri_offset, long n_vertices_out,
+                                   long n_triangles_out, float* vertices_out, float* normals_out, float* colors_out,
+                                   int32_t* triangles_out, void* stream) {
+  if (!vertices || !triangles || !keep || !used || !vert_offset || !tri_offset || n_vertices_out < 0 || n_triangles_out < 0)
+    return JT_ERR_ARG;
+  if (const int rc = mesh_filter_shape(n_vertices, n_triangles)) return rc;
+  if (n_vertices_out > n_vertices || n_triangles_out > n_triangles) return JT_ERR_ARG;
+  if (n_vertices_out == 0) return JT_OK;
+  if (!vertices_out || (n_triangles_out > 0 && !triangles_out) || (normals && !normals_out) || (colors && !colors_out))
+    return JT_ERR_ARG;
+  const long lanes = n_vertices > n_triangles ? n_vertices : n_triangles;
+  hipLaunchKernelGGL(k_mesh_filter_emit, dim3((unsigned)((lanes + kMeshThreads - 1) / kMeshThreads)), dim3(kMeshThreads), 0,
+                     (hipStream_t)stream, vertices, normals, colors, n_vertices, triangles, n_triangles, keep, used, vert_offset,
+                     tri_offset, n_vertices_out, n_triangles_out, vertices_out, normals_out, colors_out, triangles_out);
   JT_LAUNCH_CHECK();
   return JT_OK;
 }

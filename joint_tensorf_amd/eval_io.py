@@ -78,6 +78,23 @@ def normalized_invdepth(opt, invdepth_map):
     return invdepth_map
 
 
+def ndc_render_depth(depth, opacity, center_ndc, ray_ndc, pose, sx, sy, near, tf_near):
+    """Camera-axis depth [...] of what a `camera.ndc` render saw, in world units: the render's depth map is batBase.py:148-150's
+    sum w t + (1 - opacity) ray_z - tf_near + 0.05 with t the parameter along the NDC ray, so the expected parameter is
+    t = (depth + tf_near - 0.05 - (1 - opacity) ray_z) / opacity; the NDC point c + t r (c, r [..., 3]: ops.ray_gen(..., ndc=True)
+    of the same pixels) goes through the inverse NDC map (u = 1 - zn, z = 2 near / u, x = xn z / sx, y = yn z / sy) and then
+    through the world-to-camera pose [3, 4]: (R p + t)_z.  +inf where the point lies at or behind infinity (u <= 0).  Plain torch
+    in the dtype of its arguments, on whatever device they live: a report, not a hot path."""
+    t = (depth + tf_near - 0.05 - (1 - opacity) * ray_ndc[..., 2]) / opacity
+    p = center_ndc + t[..., None] * ray_ndc
+    u = 1 - p[..., 2]
+    ok = u > 0
+    z = 2 * near / torch.where(ok, u, torch.ones_like(u))
+    x, y = p[..., 0] * z / sx, p[..., 1] * z / sy
+    d = pose[2, 0] * x + pose[2, 1] * y + pose[2, 2] * z + pose[2, 3]
+    return torch.where(ok, d, torch.full_like(d, float("inf")))
+
+
 def encode_videos(output_path, frame_dir, it=None):
     """The reference's two ffmpeg commands (model/nerf.py:623-627), run only when an ffmpeg executable is on PATH."""
     exe = shutil.which("ffmpeg")

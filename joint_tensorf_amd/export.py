@@ -21,7 +21,15 @@ data.image_size), shaded by `--preview.shade=color|normal|depth`; `--preview.cul
 `--preview.check=true` also renders the field at the same cameras (OUT/preview/field_<idx>.png) and writes OUT/report.json:
 per view the coverage of mesh and field, their IoU, the median depth difference, the PSNR of the colours and what became of
 every triangle.  It reports; it judges nothing.  The preview needs the run's image set and a world-space scene (not
-`camera.ndc`).  Without a `--preview.*` option the export writes what it always wrote, byte for byte.
+`camera.ndc` whose mesh stays in NDC).  Without a `--preview.*` option the export writes what it always wrote, byte for byte.
+
+`--frame.space=world` carries the mesh of a `camera.ndc` scene out of NDC on the device (ops.ndc_to_world, ops.compact_mesh;
+csrc/jt_mesh.hip): mesh.ply then holds LLFF geometry in the frame of the refined cameras of cameras.json (`space world`, with
+`unwarp near N sx SX sy SY` and `dropped beyond B far F` comments), and `--preview.*` draws it like any world-space mesh.
+Triangles with a vertex at or behind infinity (zn >= 1: the far cap) are dropped and counted; `--frame.max_depth=D` also drops
+what lies more than D world units along the reference axis away -- forward-facing backgrounds run out to thousands of near-plane
+distances and ruin a viewer's framing.  The step needs the run's image set (sx = fx / cx, sy = fy / cy of its intrinsics).
+`--frame.space=ndc` names what an NDC export does by default; without a `--frame.*` option nothing changes.
 
 Every other `--key.sub=value` is one of the dotted overrides of joint_tensorf_amd.train."""
 import sys
@@ -37,6 +45,10 @@ SURFACE_DEFAULTS = dict(keep_largest=None, min_points=None, normals=False, color
 PREVIEW_DEFAULTS = dict(views=0, size=None, shade="color", check=False, cull=False)
 PREVIEW_SHADES = ("color", "normal", "depth")
 PREVIEW_MAX_SIZE = 16384        # what the rasteriser draws (include/jt_render.h)
+# the coordinates mesh.ply is written in (space: "world" or "ndc"; None = what the scene lives in: ndc for camera.ndc, world
+# otherwise) and, for an NDC scene exported to world, the depth along the reference axis beyond which geometry is dropped
+FRAME_DEFAULTS = dict(space=None, max_depth=None)
+FRAME_SPACES = ("world", "ndc")
 
 
 def _option_group(over, name, defaults):
@@ -62,13 +74,16 @@ def build_options(argv):
                          "[--mesh.level=L] [--mesh.cap=true|false] [--surface.keep_largest=K] [--surface.min_points=M] "
                          "[--surface.normals=true|false] [--surface.colors=true|false] [--preview.views=N|all] [--preview.size=[H,W]] "
                          "[--preview.shade=color|normal|depth] [--preview.check=true|false] [--preview.cull=true|false] "
+                         "[--frame.space=world|ndc] [--frame.max_depth=D] "
                          "[--data.root=DIR --key.sub=value ...]")
     mesh = _option_group(over, "mesh", MESH_DEFAULTS)
     surface = _option_group(over, "surface", SURFACE_DEFAULTS)
     preview = _option_group(over, "preview", PREVIEW_DEFAULTS)
+    frame = _option_group(over, "frame", FRAME_DEFAULTS)
     opt = apply_overrides(load_options(name), over)
-    opt.mesh, opt.surface, opt.preview = mesh, surface, preview
+    opt.mesh, opt.surface, opt.preview, opt.frame = mesh, surface, preview, frame
     _check_preview(preview)
+    _check_frame(frame, bool(opt.camera.ndc))
     for k in ("keep_largest", "min_points"):
         v = surface[k]
         if v is not None:
@@ -116,6 +131,27 @@ def _check_preview(preview):
                          "--preview.views=N or --preview.views=all")
 
 
+def _check_frame(frame, ndc):
+    import math
+    if frame.space is not None and frame.space not in FRAME_SPACES:
+        raise SystemExit("--frame.space is one of %s (got %r)" % (", ".join(FRAME_SPACES), frame.space))
+    d = frame.max_depth
+    if d is not None:
+        if isinstance(d, bool) or not isinstance(d, (int, float)) or not math.isfinite(d) or not d > 0:
+            raise SystemExit("--frame.max_depth is a positive finite number, in world units along the reference axis (got %r)" % (d,))
+        frame.max_depth = float(d)
+    if frame.space == "ndc" and not ndc:
+        raise SystemExit("--frame.space=ndc needs a camera.ndc scene: this one lives in world space and has no NDC coordinates")
+    if d is not None and not (ndc and frame.space == "world"):
+        raise SystemExit("--frame.max_depth limits a camera.ndc scene that is exported to world space: give it with "
+                         "--frame.space=world on such a scene")
+
+
+def unwarps(opt):
+    """whether this export carries the mesh of an NDC scene to world space (opt.frame.space == "world" on camera.ndc)"""
+    return bool(opt.camera.ndc) and (opt.get("frame", None) or {}).get("space", None) == "world"
+
+
 def has_dataset(opt):
     """whether the run names an image set (a root for the native loaders, a synthetic scene, or ready-made views)"""
     d = opt.data
@@ -129,14 +165,19 @@ def main(argv=None):
     opt = build_options(sys.argv[1:] if argv is None else list(argv))
     if not opt.get("load", None) or not opt.get("output_path", None):
         raise SystemExit("--load=CKPT and --output_path=OUT are required: the checkpoint to read, the directory to write to")
+    if unwarps(opt) and not has_dataset(opt):
+        # refused before any GPU work: the NDC map is made of the training views' intrinsics
+        raise SystemExit("--frame.space=world needs the run's image set (--data.root=DIR, or --data.synthetic=true): sx = fx / cx "
+                         "and sy = fy / cy of the NDC map are read from its intrinsics")
     if opt.preview.views != 0:
         # refused before any GPU work: the preview draws the mesh from the cameras of cameras.json
         if not has_dataset(opt):
             raise SystemExit("--preview.views needs the run's image set (--data.root=DIR, or --data.synthetic=true): without it no "
                              "cameras.json is written and there is no camera to look from")
-        if opt.camera.ndc:
+        if opt.camera.ndc and not unwarps(opt):
             raise SystemExit("--preview.views is not available for camera.ndc scenes (space ndc): the mesh lives in the scene "
-                             "box's NDC coordinates and the projective matrix that draws it there is not built yet")
+                             "box's NDC coordinates and the rasteriser's depth cannot order it there; --frame.space=world "
+                             "carries it to world space and enables the preview")
     dev = torch.device(opt.device)
     with torch.cuda.device(dev):
         m = bat_hip.Model(opt)

@@ -1076,31 +1076,55 @@ class Model(torch.nn.Module):
         centre_dataset = (centre - t1) / s1 @ R^T * s0 + t0.  opt.surface (keep_largest, min_points, normals, colors; all off
         when absent) removes floaters and adds per-vertex normals / colours to the PLY, with a `components kept K dropped D`
         and a `normals degenerate N` comment for what ran.  Returns Opt(mesh, cameras, n_vertices, n_triangles, n_components,
-        n_degenerate_normals); the last two are None for what did not run."""
+        n_degenerate_normals); the last two are None for what did not run.
+
+        opt.frame.space == "world" on an opt.camera.ndc scene carries the extracted mesh out of NDC (unwarp_mesh: normals and
+        colours are evaluated on the NDC vertices first and travel with them): the PLY and the JSON then say `space world`, with
+        `unwarp near N sx SX sy SY` and `dropped beyond B far F` comments; the result also has `unwarp` = Opt(near, sx, sy,
+        n_dropped_beyond, n_dropped_far).  That needs the training set's intrinsics: without one a ValueError before any work."""
         from .. import mesh_io
         mcfg = opt.get("mesh", None) or {}
-        space = "ndc" if opt.camera.ndc else "world"
+        unwarp = self.unwarps(opt)
+        if unwarp and self.train_data is None:
+            raise ValueError("export_scene: frame.space = world on a camera.ndc scene needs the training set (its intrinsics make "
+                             "the NDC map)")
+        space = "ndc" if opt.camera.ndc and not unwarp else "world"
         os.makedirs(directory, exist_ok=True)
         scfg = opt.get("surface", None) or {}
+        want_normals, want_colors = bool(scfg.get("normals", False)), bool(scfg.get("colors", False))
+        ext_normals, ext_colors = want_normals, want_colors
+        pcfg = opt.get("preview", None) or {}
+        if unwarp and pcfg.get("views", 0):
+            # what the preview shades with is evaluated in NDC, where the field lives, before the vertices leave it
+            shade = pcfg.get("shade", "color")
+            ext_normals = ext_normals or shade in ("color", "normal")
+            ext_colors = ext_colors or shade == "color"
         nerf = self.graph.nerf
         pe = {}
-        if scfg.get("colors", False) and getattr(nerf, "progress_host", None) is not None:
+        if ext_colors and getattr(nerf, "progress_host", None) is not None:
             # the schedule's PE masks at the model's progress, as render_rays hands them to a forward
             for key, name in (("view_pe_progress", "c2f_view_pe_schedule"), ("fea_pe_progress", "c2f_fea_pe_schedule")):
                 pe[key] = interp_schedule(nerf.progress_host, opt[name]) if _has(opt, name) else 1.0
         mesh = nerf.tensorf.extract_mesh(res=mcfg.get("res", None), level=float(mcfg.get("level", 0.005)),
                                          cap=bool(mcfg.get("cap", True)), keep_largest=scfg.get("keep_largest", None),
-                                         min_points=scfg.get("min_points", None), normals=bool(scfg.get("normals", False)),
-                                         colors=bool(scfg.get("colors", False)), **pe)
+                                         min_points=scfg.get("min_points", None), normals=ext_normals, colors=ext_colors, **pe)
+        frame = None
+        if unwarp:
+            mesh, frame = self.unwarp_mesh(opt, mesh)
         out = Opt(mesh=os.path.join(directory, "mesh.ply"), cameras=None, n_vertices=int(mesh.vertices.shape[0]),
                   n_triangles=int(mesh.triangles.shape[0]), n_components=mesh.n_components,
-                  n_degenerate_normals=mesh.n_degenerate_normals)
+                  n_degenerate_normals=mesh.n_degenerate_normals if want_normals else None)
         comments = mesh_io.mesh_comments(mesh.level, mesh.shape, mesh.lo, mesh.hi, space)
         if mesh.n_components is not None:
             comments.append("components kept %d dropped %d" % mesh.n_components)
-        if mesh.normals is not None:
+        if want_normals:
             comments.append("normals degenerate %d" % mesh.n_degenerate_normals)
-        mesh_io.write_ply(out.mesh, mesh.vertices, mesh.triangles, comments, normals=mesh.normals, colors=mesh.colors)
+        if frame is not None:
+            out.unwarp = frame
+            comments.append("unwarp near %r sx %r sy %r" % (frame.near, frame.sx, frame.sy))
+            comments.append("dropped beyond %d far %d" % (frame.n_dropped_beyond, frame.n_dropped_far))
+        mesh_io.write_ply(out.mesh, mesh.vertices, mesh.triangles, comments, normals=mesh.normals if want_normals else None,
+                          colors=mesh.colors if want_colors else None)
         if self.train_data is None:
             print("joint_tensorf_amd: export_scene without a training set: %s written, the cameras skipped" % out.mesh)
             return out
@@ -1120,6 +1144,44 @@ class Model(torch.nn.Module):
             out.preview = self.preview_scene(opt, directory, mesh=mesh)
         return out
 
+    # ---- the mesh of an NDC scene in the frame of its cameras ------------------------------------------------------
+    @staticmethod
+    def unwarps(opt):
+        """whether an export of this run carries its mesh from NDC to world space: opt.frame.space == "world" on camera.ndc"""
+        return bool(opt.camera.ndc) and (opt.get("frame", None) or {}).get("space", None) == "world"
+
+    def ndc_frame(self, opt):
+        """(sx, sy, near) of the NDC map the ray generator applies to this run's training views: sx = fx / cx and sy = fy / cy in
+        fp32 as the kernel forms them, near = opt.arch.ndc_near_plane (1.0 when absent).  Every training view must give the same
+        two quotients, exactly: there is ONE field, in ONE NDC frame.  Otherwise SystemExit naming two views that differ."""
+        if self.train_data is None:
+            raise ValueError("ndc_frame: no training set is loaded, so there are no intrinsics to read")
+        intr = self.train_data.all.intr.detach().to("cpu", torch.float32)
+        scale = torch.stack([intr[:, 0, 0] / intr[:, 0, 2], intr[:, 1, 1] / intr[:, 1, 2]], -1)
+        differ = (scale != scale[:1]).any(-1).nonzero().view(-1)
+        if differ.numel():
+            i = int(differ[0])
+            raise SystemExit("the NDC map needs one fx / cx and one fy / cy for the whole training set: view 0 has (%r, %r), view %d "
+                             "has (%r, %r)" % (float(scale[0, 0]), float(scale[0, 1]), i, float(scale[i, 0]), float(scale[i, 1])))
+        near = float(opt.arch.ndc_near_plane) if _has(opt.arch, "ndc_near_plane") else 1.0
+        return float(scale[0, 0]), float(scale[0, 1]), near
+
+    @torch.no_grad()
+    def unwarp_mesh(self, opt, mesh):
+        """extract_mesh's Mesh of a camera.ndc scene carried to world space, the frame of the refined cameras: ops.ndc_to_world
+        (ndc_frame's map, opt.frame.max_depth) on its vertices and normals, then ops.compact_mesh -- triangles with a vertex at or
+        behind infinity or beyond max_depth are dropped and counted, colours travel with their vertices.  Returns (Mesh, Opt(near,
+        sx, sy, n_dropped_beyond, n_dropped_far)); lo, hi and shape stay those of the NDC lattice the surface was taken on."""
+        sx, sy, near = self.ndc_frame(opt)
+        frame = Opt(near=near, sx=sx, sy=sy, n_dropped_beyond=0, n_dropped_far=0)
+        if mesh.vertices.shape[0] == 0:
+            return mesh, frame
+        max_depth = (opt.get("frame", None) or {}).get("max_depth", None)
+        world, normals, status = ops.ndc_to_world(mesh.vertices, sx, sy, near, normals=mesh.normals, max_depth=max_depth)
+        v, t, n, c, (frame.n_dropped_beyond, frame.n_dropped_far) = ops.compact_mesh(world, mesh.triangles, status, normals=normals,
+                                                                                   colors=mesh.colors)
+        return mesh._replace(vertices=v, triangles=t, normals=n, colors=c), frame
+
     # ---- a look at the exported mesh from the cameras it was exported with --------------------------------------
     PREVIEW_REPORT_KEYS = ("coverage_mesh", "coverage_field", "iou", "depth_abs_median", "psnr_color")
 
@@ -1136,26 +1198,42 @@ class Model(torch.nn.Module):
         (opacity >= 0.5), their iou, depth_abs_median (over pixels the mesh covers and the field renders with opacity >= 0.99;
         the field's depth with the `- near + 0.05` of batBase.py:150 undone; both are distances along the camera axis),
         psnr_color (shade color: over pixels both cover) and the five triangle counts (ops.RASTER_STATUS); then the means over
-        the views.  A value over an empty set of pixels is null and left out of its mean.  Nothing is judged: the tool reports.
+        the views.  A camera.ndc scene is drawn only as a world-space mesh (opt.frame.space == "world": a given mesh is
+        unwarp_mesh's, one extracted here goes through it); its render's depth is carried to the camera axis in world units
+        (eval_io.ndc_render_depth) and the report gains disparity_abs_median, the median |1/d_mesh - 1/d_field| over the same pixels.  A value over an empty set of pixels is null and left out of its mean.  Nothing is judged: the tool reports.
 
         Returns Opt(directory, views: the indices drawn, report: the path or None, means: the dict or None, summary: one line)."""
         import json
         from .. import eval_io, mesh_io
         cfg = opt.preview
-        if opt.camera.ndc:
+        unwarp = self.unwarps(opt)
+        if opt.camera.ndc and not unwarp:
             raise ValueError("preview_scene: camera.ndc scenes (space ndc) are not drawn: the mesh lives in the scene box's NDC "
-                             "coordinates and the projective matrix for it is not built yet")
+                             "coordinates and the rasteriser's depth cannot order it there; frame.space = world (--frame.space=world) "
+                             "carries it to world space and enables the preview")
         if self.train_data is None:
             raise ValueError("preview_scene: no training set is loaded, so there is no camera to look from")
         nerf = self.graph.nerf
         tf = nerf.tensorf
-        if mesh is None:
-            mcfg, scfg = opt.get("mesh", None) or {}, opt.get("surface", None) or {}
-            mesh = tf.extract_mesh(res=mcfg.get("res", None), level=float(mcfg.get("level", 0.005)), cap=bool(mcfg.get("cap", True)),
-                                   keep_largest=scfg.get("keep_largest", None), min_points=scfg.get("min_points", None))
         shade = cfg.get("shade", "color")
         if shade not in ("color", "normal", "depth"):
             raise ValueError("preview_scene: shade is color, normal or depth (got %r)" % (shade,))
+        if mesh is None:
+            mcfg, scfg = opt.get("mesh", None) or {}, opt.get("surface", None) or {}
+            extra = {}
+            if unwarp:
+                # normals and colours are the field's, and the field lives in NDC: evaluated there, carried over by unwarp_mesh
+                extra = dict(normals=shade in ("color", "normal"), colors=shade == "color")
+                if shade == "color" and getattr(nerf, "progress_host", None) is not None:
+                    for key, name in (("view_pe_progress", "c2f_view_pe_schedule"), ("fea_pe_progress", "c2f_fea_pe_schedule")):
+                        extra[key] = interp_schedule(nerf.progress_host, opt[name]) if _has(opt, name) else 1.0
+            mesh = tf.extract_mesh(res=mcfg.get("res", None), level=float(mcfg.get("level", 0.005)), cap=bool(mcfg.get("cap", True)),
+                                   keep_largest=scfg.get("keep_largest", None), min_points=scfg.get("min_points", None), **extra)
+            if unwarp:
+                mesh = self.unwarp_mesh(opt, mesh)[0]
+        if unwarp and ((shade in ("color", "normal") and mesh.normals is None) or (shade == "color" and mesh.colors is None)):
+            raise ValueError("preview_scene: a world-space mesh of a camera.ndc scene must bring the normals / colours it is shaded "
+                             "with (they are evaluated in NDC, before unwarp_mesh)")
         if mesh.triangles.shape[0] == 0:
             raise ValueError("preview_scene: the mesh is empty (level %r): nothing to draw" % (mesh.level,))
         pose, _ = self.get_all_training_poses(opt)
@@ -1188,8 +1266,12 @@ class Model(torch.nn.Module):
         invdepth = torch.where(covered, 1 / drawn.depth, torch.zeros_like(drawn.depth))
         path = os.path.join(directory, "preview")
         os.makedirs(path, exist_ok=True)
+
+        def invdepth_picture(x):
+            # (a world-space mesh of an NDC scene shows its plain inverse world depth: the NDC normalisation is the render's)
+            return x if unwarp else eval_io.normalized_invdepth(opt, x)
         for j, i in enumerate(idx):
-            picture = (eval_io.normalized_invdepth(opt, invdepth[j][None]) if shade == "depth" else drawn.attrs[j].permute(2, 0, 1))
+            picture = (invdepth_picture(invdepth[j][None]) if shade == "depth" else drawn.attrs[j].permute(2, 0, 1))
             eval_io.save_png(picture, os.path.join(path, "mesh_%d.png" % i))
         out = Opt(directory=path, views=idx, report=None, means=None,
                   summary="preview of %d views at %d x %d in %s" % (len(idx), H, W, path))
@@ -1204,14 +1286,26 @@ class Model(torch.nn.Module):
         size0 = (opt.H, opt.W)
         rows = []
         counts = drawn.status_counts.tolist()
+        keys = self.PREVIEW_REPORT_KEYS + (("disparity_abs_median",) if unwarp else ())
+        if unwarp:
+            sx, sy, ndc_near = self.ndc_frame(opt)
+            pixels = torch.arange(H * W, device=pose.device)
         try:
             opt.H, opt.W = H, W
             for j, i in enumerate(idx):
                 ret = self.graph.render_by_slices(opt, pose[j:j + 1], intr_inv=intr_inv[j:j + 1], intr=intr_s[j:j + 1])
                 opacity = ret.opacity.view(H, W)
                 rgb = ret.rgb.view(H, W, 3)
-                depth_f = ret.depth.view(H, W) + float(tf.near_far[0]) - 0.05      # (the near plane this render marched from)
-                if shade == "depth":
+                if unwarp:
+                    # the NDC render's depth is a parameter along the NDC ray: carried to the camera's axis in world units
+                    center, ray = ops.ray_gen(pose[j:j + 1], intr_inv[j:j + 1], intr_s[j:j + 1], pixels, W, ndc=True, ndc_near=ndc_near)
+                    depth_f = eval_io.ndc_render_depth(ret.depth.view(-1), ret.opacity.view(-1), center[0], ray[0], pose[j], sx, sy,
+                                                       ndc_near, float(tf.near_far[0])).view(H, W)
+                else:
+                    depth_f = ret.depth.view(H, W) + float(tf.near_far[0]) - 0.05      # (the near plane this render marched from)
+                if shade == "depth" and unwarp:
+                    picture = torch.where(torch.isfinite(depth_f) & (depth_f > 0), 1 / depth_f, torch.zeros_like(depth_f))[None]
+                elif shade == "depth":
                     picture = eval_io.normalized_invdepth(opt, (1 / (ret.depth.view(H, W) / opacity + 1e-10))[None])
                 else:
                     picture = rgb.permute(2, 0, 1)
@@ -1219,6 +1313,8 @@ class Model(torch.nn.Module):
                 m, f = covered[j], opacity >= 0.5
                 union = (m | f).sum()
                 solid = m & (opacity >= 0.99)
+                if unwarp:
+                    solid = solid & torch.isfinite(depth_f) & (depth_f > 0)
                 both = m & f
                 row = {"idx": i, "coverage_mesh": float(m.float().mean()), "coverage_field": float(f.float().mean()),
                        "iou": float((m & f).sum() / union) if int(union) else 1.0,
@@ -1227,12 +1323,16 @@ class Model(torch.nn.Module):
                 if shade == "color" and int(both.sum()):
                     mse = ((drawn.attrs[j] - rgb)[both] ** 2).mean().clamp(min=1e-10)
                     row["psnr_color"] = float(-10 * torch.log10(mse))
+                if unwarp:
+                    # depth differences out to infinity say little: the same pixels in inverse depth
+                    row["disparity_abs_median"] = (float((1 / drawn.depth[j] - 1 / depth_f)[solid].abs().median())
+                                                   if int(solid.sum()) else None)
                 row["triangles"] = dict(zip(ops.RASTER_STATUS, (int(c) for c in counts[j])))
                 rows.append(row)
         finally:
             opt.H, opt.W = size0
         means = {}
-        for key in self.PREVIEW_REPORT_KEYS:
+        for key in keys:
             vals = [r[key] for r in rows if r[key] is not None]
             means[key] = sum(vals) / len(vals) if vals else None
         means["triangles"] = {s: sum(r["triangles"][s] for r in rows) / len(rows) for s in ops.RASTER_STATUS}
@@ -1251,6 +1351,8 @@ class Model(torch.nn.Module):
                        % (len(idx), H, W, show(means["coverage_mesh"], "%.3f"), show(means["coverage_field"], "%.3f"),
                           show(means["iou"], "%.3f"), show(means["depth_abs_median"], "%.4f"), show(means["psnr_color"], "%.2f dB"),
                           round(means["triangles"]["drawn"]), mesh.triangles.shape[0], out.report))
+        if unwarp:
+            out.summary += "; median disparity difference %s" % show(means["disparity_abs_median"], "%.5f")
         return out
 
     # ---- evaluation ---------------------------------------------------------------------------

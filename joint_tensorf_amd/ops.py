@@ -1574,6 +1574,88 @@ def cap_lattice(vol, lo, hi):
     return torch.nn.functional.pad(vol, (1, 1, 1, 1, 1, 1)), (lo - unit).tolist(), (hi + unit).tolist()
 
 
+# what jt_mesh_unwarp_ndc's status bytes say (include/jt_render.h: JT_UNWARP_*)
+UNWARP_STATUS = ("kept", "beyond", "far")
+
+
+def ndc_to_world(vertices, sx, sy, near, normals=None, max_depth=None):
+    """Vertices [n, 3] fp32 of an NDC scene (xn = sx x/z, yn = sy y/z, zn = 1 - 2 near/z, as the ray generator has it) carried to
+    world space on the device (jt_mesh_unwarp_ndc, one launch): (world [n, 3], world_normals [n, 3] or None without `normals`
+    [n, 3], status [n] uint8: 0 kept, 1 beyond (non-finite, at or behind infinity: zn >= 1), 2 far (max_depth given and z >
+    max_depth)).  u = 1 - zn, z = 2 near / u, x = xn z / sx, y = yn z / sy; a normal goes through J^T: (sx nx, sy ny, u nz - xn nx
+    - yn ny) normalised, (0, 0, 0) staying (0, 0, 0).  A vertex that is not kept comes back as zeros."""
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.shape[0] < 1:
+        raise ValueError("ndc_to_world: vertices are [n, 3] with n >= 1 (got %s)" % (tuple(vertices.shape),))
+    vertices = vertices.detach().contiguous().float()
+    n = vertices.shape[0]
+    if normals is not None:
+        if tuple(normals.shape) != (n, 3):
+            raise ValueError("ndc_to_world: one normal per vertex (got %s for %d vertices)" % (tuple(normals.shape), n))
+        normals = normals.detach().contiguous().float()
+    if max_depth is not None and not (float(max_depth) > 0 and math.isfinite(float(max_depth))):
+        raise ValueError("ndc_to_world: max_depth is a positive finite number or None (got %r)" % (max_depth,))
+    world = torch.empty_like(vertices)
+    world_normals = torch.empty_like(normals) if normals is not None else None
+    status = torch.empty(n, device=vertices.device, dtype=torch.uint8)
+    check(lib.jt_mesh_unwarp_ndc(ptr(vertices), ptr(normals), n, float(sx), float(sy), float(near),
+                                 0.0 if max_depth is None else float(max_depth), ptr(world), ptr(world_normals), ptr(status),
+                                 _stream()), "jt_mesh_unwarp_ndc")
+    return world, world_normals, status
+
+
+def compact_mesh(vertices, triangles, status, normals=None, colors=None):
+    """The mesh without the triangles that have a vertex of status != 0 (ndc_to_world's) or an id out of range, and without the
+    vertices no kept triangle names: (vertices' [nv', 3], triangles' [nt', 3] int32 with remapped ids, normals' or None, colors' or
+    None, (n_dropped_beyond, n_dropped_far)) -- a dropped triangle is counted once, by the first that applies of beyond, far.
+    jt_mesh_filter_count, two cumsums, ONE host read (the two sizes and the two counts), jt_mesh_filter_emit: triangles and
+    vertices keep their order, two calls return the same bits.  Empty results are [0, 3] tensors."""
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or triangles.dim() != 2 or triangles.shape[1] != 3:
+        raise ValueError("compact_mesh: vertices are [nv, 3] and triangles [nt, 3] (got %s, %s)" % (tuple(vertices.shape), tuple(triangles.shape)))
+    if triangles.dtype != torch.int32:
+        raise ValueError("compact_mesh: triangles are int32 vertex ids (got %s)" % triangles.dtype)
+    nv, nt = vertices.shape[0], triangles.shape[0]
+    if status.dtype != torch.uint8 or tuple(status.shape) != (nv,):
+        raise ValueError("compact_mesh: status is uint8 [nv] (got %s %s for %d vertices)" % (status.dtype, tuple(status.shape), nv))
+    dev = vertices.device
+    vertices = vertices.detach().contiguous().float()
+    triangles = triangles.detach().contiguous()
+    status = status.contiguous()
+    attrs = []
+    for name, a in (("normals", normals), ("colors", colors)):
+        if a is not None:
+            if tuple(a.shape) != (nv, 3):
+                raise ValueError("compact_mesh: %s are [nv, 3] (got %s for %d vertices)" % (name, tuple(a.shape), nv))
+            a = a.detach().contiguous().float()
+        attrs.append(a)
+    normals, colors = attrs
+
+    def empty():
+        return (vertices.new_empty(0, 3), triangles.new_empty(0, 3), None if normals is None else normals.new_empty(0, 3),
+                None if colors is None else colors.new_empty(0, 3))
+    if nv == 0 or nt == 0:
+        return empty() + ((0, 0),)
+    keep = torch.empty(nt, device=dev, dtype=torch.uint8)
+    cause = torch.empty(nt, device=dev, dtype=torch.uint8)
+    used = torch.zeros(nv, device=dev, dtype=torch.uint8)
+    check(lib.jt_mesh_filter_count(ptr(triangles), nt, ptr(status), nv, ptr(keep), ptr(cause), ptr(used), _stream()),
+          "jt_mesh_filter_count")
+    vert_end = torch.cumsum(used, 0, dtype=torch.int64)
+    tri_end = torch.cumsum(keep, 0, dtype=torch.int64)
+    nv_out, nt_out, n_beyond, n_far = (int(v) for v in torch.stack([vert_end[-1], tri_end[-1], (cause == 1).sum(),
+                                                                    (cause == 2).sum()]).tolist())
+    if nt_out == 0:
+        return empty() + ((n_beyond, n_far),)
+    vert_offset, tri_offset = vert_end.sub_(used), tri_end.sub_(keep)
+    v_out = torch.empty(nv_out, 3, device=dev, dtype=torch.float32)
+    t_out = torch.empty(nt_out, 3, device=dev, dtype=torch.int32)
+    n_out = torch.empty(nv_out, 3, device=dev, dtype=torch.float32) if normals is not None else None
+    c_out = torch.empty(nv_out, 3, device=dev, dtype=torch.float32) if colors is not None else None
+    check(lib.jt_mesh_filter_emit(ptr(vertices), ptr(normals), ptr(colors), nv, ptr(triangles), nt, ptr(keep), ptr(used),
+                                  ptr(vert_offset), ptr(tri_offset), nv_out, nt_out, ptr(v_out), ptr(n_out), ptr(c_out), ptr(t_out),
+                                  _stream()), "jt_mesh_filter_emit")
+    return v_out, t_out, n_out, c_out, (n_beyond, n_far)
+
+
 # points per edge of the tile a workgroup of the component sweep owns (include/jt_render.h: JT_COMPONENTS_TILE)
 COMPONENTS_TILE = 8
 # Sweeps after which lattice_components gives up.  Measured with pointer jumping (profiles/mesh_surface_export.txt): the two
