@@ -42,9 +42,9 @@ extern "C" {
  * jt_image_ingest / jt_image_ingest_workspace_bytes; 1207: + jt_shade_backward_plan / jt_march_backward_plan; 1208: + jt_mesh_count / jt_mesh_emit;
  * 1209: + jt_components_init / jt_components_sweep / jt_component_sizes, jt_density_gradient, JT_COMPONENTS_TILE; 1210: +
  * jt_raster_project / jt_raster_draw / jt_raster_resolve, JT_RASTER_*; 1211: + jt_mesh_unwarp_ndc / jt_mesh_filter_count / jt_mesh_filter_emit,
- * JT_UNWARP_*.  Additions bump the last two digits, anything a caller built against the old header would get wrong bumps the
- * hundreds). */
-#define JT_VERSION 1211
+ * JT_UNWARP_*; 1212: + jt_simplify_keys / jt_simplify_clusters / jt_simplify_triangles, JT_SIMPLIFY_*.  Additions bump the last two
+ * digits, anything a caller built against the old header would get wrong bumps the hundreds). */
+#define JT_VERSION 1212
 
 #define JT_OK 0
 #define JT_ERR_ARG 1         /* null pointer / bad size */
@@ -650,6 +650,66 @@ int jt_mesh_filter_emit(const float* vertices, const float* normals, const float
                         const int32_t* triangles, long n_triangles, const uint8_t* keep, const uint8_t* used,
                         const int64_t* vert_offset, const int64_t* tri_offset, long n_vertices_out, long n_triangles_out,
                         float* vertices_out, float* normals_out, float* colors_out, int32_t* triangles_out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Mesh simplification (csrc/jt_simplify.hip): vertex clustering with a quadric (Hermite) representative.  Vertices are binned
+ * into a uniform grid of cells3 = (cx, cy, cz) cells over the box lo3 .. hi3 (HOST pointers, as jt_mesh_emit takes them; cells3 a
+ * HOST pointer to three ints); every occupied cell becomes ONE vertex, placed where the planes (position, normal) of its members
+ * meet in the least-squares sense, regularised towards their mean; triangles are re-indexed and the collapsed ones dropped.  No
+ * atomics, the same bits on every run, and every number below is a fixed sequence of correctly rounded operations (no
+ * contraction): a NumPy statement of this comment reproduces the kernels bit for bit (tests/simplify_ref.py).
+ *
+ *   jt_simplify_keys: keys [n] int64 of vertices [n][3] fp32.  Per axis, in fp32, four operations each rounded once:
+ *       d = x - lo,  w = hi - lo,  s = d / w,  f = s * float(cells);   i = cells - 1 if f >= cells, 0 if f < 0, else floorf(f);
+ *     key = (ix * cy + iy) * cz + iz.  A vertex with a non-finite coordinate gets key cx * cy * cz, the "none" cluster, which owns
+ *     no output vertex.
+ *   the caller sorts the keys STABLY (members of a cluster stay in ascending vertex id) into order [n] int64, the vertex ids in
+ *     sorted order; cluster j is the j-th distinct key below cx cy cz in ascending order and seg_start [n_clusters + 1] int64 the
+ *     positions in `order` where the clusters begin, seg_start[n_clusters] = the number of vertices with a key below cx cy cz.
+ *   jt_simplify_clusters: one lane per cluster, walking its members v_1 < ... < v_m = order[seg_start[j] .. seg_start[j + 1]) in
+ *     that order (a wave per cluster would sum in another order: the order IS the contract).  Everything in fp64 from the fp32
+ *     inputs, every sum sequential from 0.0 in member order, p = position, n = normal with (0, 0, 0) for one that has a non-finite
+ *     component:
+ *       c = (sum p_v) / m                                           per axis;
+ *       per member  d = p_v - c,  e = (n_x d_x + n_y d_y) + n_z d_z,
+ *                   a00 += n_x n_x, a01 += n_x n_y, a02 += n_x n_z, a11 += n_y n_y, a12 += n_y n_z, a22 += n_z n_z,
+ *                   b += n e  and  sn += n                          per axis;
+ *       r = double(lambda) * m;  a00 += r, a11 += r, a22 += r;
+ *       k00 = a11 a22 - a12 a12,  k01 = a02 a12 - a01 a22,  k02 = a01 a12 - a02 a11,
+ *       k11 = a00 a22 - a02 a02,  k12 = a01 a02 - a00 a12,  k22 = a00 a11 - a01 a01     (each: two products, one difference),
+ *       det = (a00 k00 + a01 k01) + a02 k02,
+ *       x0 = ((k00 b0 + k01 b1) + k02 b2) / det,  x1 = ((k01 b0 + k11 b1) + k12 b2) / det,  x2 = ((k02 b0 + k12 b1) + k22 b2) / det;
+ *       positions[j] = min(max(fp32(c + x), lowest member coordinate), highest member coordinate)   per axis, min / max in fp32.
+ *     A is positive definite with a condition number of at most (1 + lambda) / lambda for unit normals: no pivoting.  With unit
+ *     normals this is the dual-contouring QEF regularised towards the mean: flat, zero-normal and single-normal clusters give the
+ *     mean (along the directions the normals do not fix).  A representative never leaves the bounding box of what it replaces,
+ *     and a cluster of one member returns its vertex exactly.  normals_out[j] = fp32(sn / sqrt((sn_x sn_x + sn_y sn_y) + sn_z
+ *     sn_z)) per axis, (0, 0, 0) when the length is zero or not finite; counts[j] = m (int32).  An `order` entry outside [0, n)
+ *     is no member and seg_start is clamped to [0, n]: nothing is read out of bounds; an empty cluster is written as zeros.
+ *   the caller scatters the cluster index over `order` into cluster [n] int32, -1 for the none cluster;
+ *   jt_simplify_triangles: per triangle of triangles [n_triangles][3] triangles_out[t] = (cluster[a], cluster[b], cluster[c]), -1
+ *     for an id outside [0, n_vertices) or a cluster outside [0, n_clusters); cause[t] = the first that applies of
+ *       JT_SIMPLIFY_INVALID 1: an id out of range or a vertex of the none cluster;
+ *       JT_SIMPLIFY_COLLAPSED 2: two of the three clusters equal;
+ *       JT_SIMPLIFY_KEPT 0;
+ *     keep[t] = 1 for a kept one, and used[j] = 1 for the clusters of kept triangles (used [n_clusters], zeroed by the caller;
+ *     several lanes may store the same 1; no atomics).  Duplicate triangles and opposite pairs are NOT removed, deliberately: the
+ *     vertex map is simplicial, so every directed edge of the result occurs as often as its reverse whenever that held for the
+ *     input, and removing same-orientation duplicates would break it.
+ *   the caller scans keep and used and compacts with jt_mesh_filter_emit (vertices = positions, triangles = triangles_out): kept
+ *     triangles in their original order, used clusters in key order.
+ * One launch each on `stream`, nothing else; every argument is checked before the launch.  JT_ERR_ARG for a NULL pointer, a count
+ * below 1, n_clusters above the vertex count, a cell count outside 1 .. 2^20, hi <= lo on an axis, a non-finite box (or fp32
+ * extent), or a lambda that is not a positive finite number; JT_ERR_UNSUPPORTED when n (n_vertices) or 3 n_triangles reaches 2^31. */
+#define JT_SIMPLIFY_KEPT 0
+#define JT_SIMPLIFY_INVALID 1
+#define JT_SIMPLIFY_COLLAPSED 2
+int jt_simplify_keys(const float* vertices, long n, const float* lo3, const float* hi3, const int* cells3, int64_t* keys,
+                     void* stream);
+int jt_simplify_clusters(const float* vertices, const float* normals, long n, const int64_t* order, const int64_t* seg_start,
+                         long n_clusters, float lambda, float* positions, float* normals_out, int32_t* counts, void* stream);
+int jt_simplify_triangles(const int32_t* triangles, long n_triangles, const int32_t* cluster, long n_vertices, long n_clusters,
+                          int32_t* triangles_out, uint8_t* keep, uint8_t* cause, uint8_t* used, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Connected components of a lattice's inside points (csrc/jt_components.hip), with the connectivity of the mesh above: two

@@ -142,6 +142,9 @@ SIGNATURES = {
     "jt_mesh_unwarp_ndc": (I, [P, P, ctypes.c_long, F, F, F, F, P, P, P, P]),
     "jt_mesh_filter_count": (I, [P, ctypes.c_long, P, ctypes.c_long, P, P, P, P]),
     "jt_mesh_filter_emit": (I, [P, P, P, ctypes.c_long, P, ctypes.c_long, P, P, P, P, ctypes.c_long, ctypes.c_long, P, P, P, P, P]),
+    "jt_simplify_keys": (I, [P, ctypes.c_long, P, P, P, P, P]),
+    "jt_simplify_clusters": (I, [P, P, ctypes.c_long, P, P, ctypes.c_long, F, P, P, P, P]),
+    "jt_simplify_triangles": (I, [P, ctypes.c_long, P, ctypes.c_long, ctypes.c_long, P, P, P, P, P]),
     "jt_components_init": (I, [P, I, I, I, F, P, P]),
     "jt_components_sweep": (I, [P, I, I, I, P, I, P]),
     "jt_component_sizes": (I, [P, I, I, I, P, P]),
@@ -190,7 +193,7 @@ def fused_lib():
 # the JT_VERSION of include/jt_render.h that SIGNATURES and the struct mirrors above were written against.  A constant, not a
 # read of the header at import time: a vendored copy of the package has no include/ directory beside it (tests/test_abi.py
 # holds this number, the header's and the library's together)
-JT_ABI_VERSION = 1211
+JT_ABI_VERSION = 1212
 
 
 def header_version():

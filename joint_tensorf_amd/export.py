@@ -31,6 +31,16 @@ what lies more than D world units along the reference axis away -- forward-facin
 distances and ruin a viewer's framing.  The step needs the run's image set (sx = fx / cx, sy = fy / cy of its intrinsics).
 `--frame.space=ndc` names what an NDC export does by default; without a `--frame.*` option nothing changes.
 
+`--simplify.cell=K` (a number >= 1) simplifies the mesh on the device by vertex clustering (ops.simplify_mesh;
+csrc/jt_simplify.hip): the vertices that fall into one cell of K lattice spacings -- ceil((points - 1) / K) cells per axis over
+the box of the lattice -- become ONE vertex, placed where the planes (vertex, field normal) of its members meet in the
+least-squares sense and never outside their bounding box; triangles are re-indexed and the collapsed ones dropped.  It runs in
+the frame the field lives in, before `--frame.space=world` carries an NDC mesh out (cells are then perspective-sized);
+`--surface.normals` writes the clusters' normals and `--surface.colors` evaluates the colours at the simplified vertices.
+mesh.ply gains the comment `simplify cell K cells CX CY CZ from NV NT collapsed C`, report.json the same numbers, and
+`--preview.*` / `--preview.check` draw and score the simplified mesh.  Without a `--simplify.*` option mesh.ply is what it was,
+byte for byte.
+
 Every other `--key.sub=value` is one of the dotted overrides of joint_tensorf_amd.train."""
 import sys
 
@@ -49,6 +59,8 @@ PREVIEW_MAX_SIZE = 16384        # what the rasteriser draws (include/jt_render.h
 # otherwise) and, for an NDC scene exported to world, the depth along the reference axis beyond which geometry is dropped
 FRAME_DEFAULTS = dict(space=None, max_depth=None)
 FRAME_SPACES = ("world", "ndc")
+# the simplification of the extracted mesh by vertex clustering (cell: the edge of a cell in lattice spacings, None = off)
+SIMPLIFY_DEFAULTS = dict(cell=None)
 
 
 def _option_group(over, name, defaults):
@@ -74,15 +86,17 @@ def build_options(argv):
                          "[--mesh.level=L] [--mesh.cap=true|false] [--surface.keep_largest=K] [--surface.min_points=M] "
                          "[--surface.normals=true|false] [--surface.colors=true|false] [--preview.views=N|all] [--preview.size=[H,W]] "
                          "[--preview.shade=color|normal|depth] [--preview.check=true|false] [--preview.cull=true|false] "
-                         "[--frame.space=world|ndc] [--frame.max_depth=D] "
+                         "[--frame.space=world|ndc] [--frame.max_depth=D] [--simplify.cell=K] "
                          "[--data.root=DIR --key.sub=value ...]")
     mesh = _option_group(over, "mesh", MESH_DEFAULTS)
     surface = _option_group(over, "surface", SURFACE_DEFAULTS)
     preview = _option_group(over, "preview", PREVIEW_DEFAULTS)
     frame = _option_group(over, "frame", FRAME_DEFAULTS)
+    simplify = _option_group(over, "simplify", SIMPLIFY_DEFAULTS)
     opt = apply_overrides(load_options(name), over)
-    opt.mesh, opt.surface, opt.preview, opt.frame = mesh, surface, preview, frame
+    opt.mesh, opt.surface, opt.preview, opt.frame, opt.simplify = mesh, surface, preview, frame, simplify
     _check_preview(preview)
+    _check_simplify(simplify)
     _check_frame(frame, bool(opt.camera.ndc))
     for k in ("keep_largest", "min_points"):
         v = surface[k]
@@ -145,6 +159,15 @@ def _check_frame(frame, ndc):
     if d is not None and not (ndc and frame.space == "world"):
         raise SystemExit("--frame.max_depth limits a camera.ndc scene that is exported to world space: give it with "
                          "--frame.space=world on such a scene")
+
+
+def _check_simplify(simplify):
+    import math
+    k = simplify.cell
+    if k is not None:
+        if isinstance(k, bool) or not isinstance(k, (int, float)) or not math.isfinite(k) or not k >= 1:
+            raise SystemExit("--simplify.cell is a finite number of at least 1, the edge of a cell in lattice spacings (got %r)" % (k,))
+        simplify.cell = float(k)
 
 
 def unwarps(opt):

@@ -1081,7 +1081,14 @@ class Model(torch.nn.Module):
         opt.frame.space == "world" on an opt.camera.ndc scene carries the extracted mesh out of NDC (unwarp_mesh: normals and
         colours are evaluated on the NDC vertices first and travel with them): the PLY and the JSON then say `space world`, with
         `unwarp near N sx SX sy SY` and `dropped beyond B far F` comments; the result also has `unwarp` = Opt(near, sx, sy,
-        n_dropped_beyond, n_dropped_far).  That needs the training set's intrinsics: without one a ValueError before any work."""
+        n_dropped_beyond, n_dropped_far).  That needs the training set's intrinsics: without one a ValueError before any work.
+
+        opt.simplify.cell = K (a number >= 1, in lattice spacings; absent or None: off) simplifies the mesh on the device
+        (extract_mesh(simplify=K): vertex clustering in cells of K lattice spacings, csrc/jt_simplify.hip) in the frame the field
+        lives in -- NDC for a camera.ndc scene, where the cells are perspective-sized, before unwarp_mesh carries it out; normals
+        are then the clusters', colours evaluated at the simplified vertices.  The PLY gains the comment `simplify cell K cells
+        CX CY CZ from NV NT collapsed C` and the result `simplified` = (cells, n_vertices_in, n_triangles_in,
+        n_dropped_invalid, n_collapsed), which preview_scene's report.json repeats."""
         from .. import mesh_io
         mcfg = opt.get("mesh", None) or {}
         unwarp = self.unwarps(opt)
@@ -1107,7 +1114,8 @@ class Model(torch.nn.Module):
                 pe[key] = interp_schedule(nerf.progress_host, opt[name]) if _has(opt, name) else 1.0
         mesh = nerf.tensorf.extract_mesh(res=mcfg.get("res", None), level=float(mcfg.get("level", 0.005)),
                                          cap=bool(mcfg.get("cap", True)), keep_largest=scfg.get("keep_largest", None),
-                                         min_points=scfg.get("min_points", None), normals=ext_normals, colors=ext_colors, **pe)
+                                         min_points=scfg.get("min_points", None), normals=ext_normals, colors=ext_colors,
+                                         simplify=(opt.get("simplify", None) or {}).get("cell", None), **pe)
         frame = None
         if unwarp:
             mesh, frame = self.unwarp_mesh(opt, mesh)
@@ -1119,6 +1127,10 @@ class Model(torch.nn.Module):
             comments.append("components kept %d dropped %d" % mesh.n_components)
         if want_normals:
             comments.append("normals degenerate %d" % mesh.n_degenerate_normals)
+        if mesh.simplified is not None:
+            out.simplified = mesh.simplified
+            comments.append("simplify cell %g cells %d %d %d from %d %d collapsed %d"
+                            % ((float(opt.simplify.cell),) + tuple(mesh.simplified[0]) + tuple(mesh.simplified[1:3]) + (mesh.simplified[4],)))
         if frame is not None:
             out.unwarp = frame
             comments.append("unwarp near %r sx %r sy %r" % (frame.near, frame.sx, frame.sy))
@@ -1228,7 +1240,8 @@ class Model(torch.nn.Module):
                     for key, name in (("view_pe_progress", "c2f_view_pe_schedule"), ("fea_pe_progress", "c2f_fea_pe_schedule")):
                         extra[key] = interp_schedule(nerf.progress_host, opt[name]) if _has(opt, name) else 1.0
             mesh = tf.extract_mesh(res=mcfg.get("res", None), level=float(mcfg.get("level", 0.005)), cap=bool(mcfg.get("cap", True)),
-                                   keep_largest=scfg.get("keep_largest", None), min_points=scfg.get("min_points", None), **extra)
+                                   keep_largest=scfg.get("keep_largest", None), min_points=scfg.get("min_points", None),
+                                   simplify=(opt.get("simplify", None) or {}).get("cell", None), **extra)
             if unwarp:
                 mesh = self.unwarp_mesh(opt, mesh)[0]
         if unwarp and ((shade in ("color", "normal") and mesh.normals is None) or (shade == "color" and mesh.colors is None)):
@@ -1338,6 +1351,8 @@ class Model(torch.nn.Module):
         means["triangles"] = {s: sum(r["triangles"][s] for r in rows) / len(rows) for s in ops.RASTER_STATUS}
         report = {"mesh": "mesh.ply", "cameras": "cameras.json", "size": [H, W], "shade": shade, "cull": bool(cfg.get("cull", False)),
                   "n_triangles": int(mesh.triangles.shape[0]), "views": rows, "mean": means}
+        if mesh.simplified is not None:
+            report["simplified"] = [list(mesh.simplified[0])] + [int(v) for v in mesh.simplified[1:]]
         out.report = os.path.join(directory, "report.json")
         with open(out.report, "w") as fh:
             json.dump(report, fh, indent=1)

@@ -1656,6 +1656,161 @@ def compact_mesh(vertices, triangles, status, normals=None, colors=None):
     return v_out, t_out, n_out, c_out, (n_beyond, n_far)
 
 
+# the regularisation of simplify_mesh's quadric towards the cluster mean (include/jt_render.h: lambda)
+SIMPLIFY_REGULAR = 1.0 / 16.0
+SIMPLIFY_MAX_CELLS = 1 << 20
+
+
+def simplify_cells(cells):
+    """`cells` of simplify_mesh as three ints: one int (the same on every axis) or three, each in 1 .. 2^20"""
+    given = cells
+    if torch.is_tensor(cells):
+        cells = cells.tolist()
+    if not isinstance(cells, (list, tuple)):
+        cells = [cells] * 3
+    if (len(cells) != 3 or any(isinstance(c, bool) or float(c) != int(c) for c in cells)
+            or not all(1 <= int(c) <= SIMPLIFY_MAX_CELLS for c in cells)):
+        raise ValueError("simplify_mesh: cells is one int or three, each from 1 to %d (got %r)" % (SIMPLIFY_MAX_CELLS, given))
+    return [int(c) for c in cells]
+
+
+def simplify_keys(vertices, lo, hi, cells):
+    """jt_simplify_keys: the cell key [n] int64 of every vertex of vertices [n, 3] fp32 (cx cy cz for a non-finite one), one launch"""
+    keys = torch.empty(vertices.shape[0], device=vertices.device, dtype=torch.int64)
+    check(lib.jt_simplify_keys(ptr(vertices), vertices.shape[0], (ctypes.c_float * 3)(*lo), (ctypes.c_float * 3)(*hi),
+                               (ctypes.c_int * 3)(*cells), ptr(keys), _stream()), "jt_simplify_keys")
+    return keys
+
+
+def simplify_segments(keys, none_key):
+    """the caller's sort and scan between jt_simplify_keys and jt_simplify_clusters, all on the device: (order [n] int64: vertex
+    ids sorted stably by key, head [n] bool: sorted positions where a cluster begins, cid [n] int64: cluster index of every
+    sorted position, valid [n] bool: positions with a key below none_key, totals [2] int64 = (n_clusters, n_valid))"""
+    ks, order = torch.sort(keys, stable=True)
+    valid = ks < none_key
+    head = torch.ones_like(valid)
+    head[1:] = ks[1:] != ks[:-1]
+    head &= valid
+    cid = torch.cumsum(head, 0, dtype=torch.int64)
+    totals = torch.stack([cid[-1], valid.sum()])
+    return order, head, cid.sub_(1), valid, totals
+
+
+def _masked_rows(values, mask, offsets, n_out):
+    """values[mask] when offsets is the exclusive scan of mask and n_out its total, without the host read of a boolean index:
+    rows that are not wanted go to a slot past the end"""
+    out = values.new_empty((n_out + 1,) + tuple(values.shape[1:]))
+    out[torch.where(mask, offsets, torch.full_like(offsets, n_out))] = values
+    return out[:n_out]
+
+
+def simplify_mesh(vertices, triangles, normals, lo, hi, cells, regular=SIMPLIFY_REGULAR):
+    """The mesh simplified by vertex clustering on the device (csrc/jt_simplify.hip): vertices [nv, 3] fp32 are binned into a
+    uniform grid of `cells` (one int or three, each 1 .. 2^20) cells over the box lo .. hi (three floats each; a vertex outside
+    is clamped into the border cells), every occupied cell becomes one vertex -- where the planes (vertex, normal) of its members
+    meet in the least-squares sense, regularised towards their mean by `regular`, never outside the members' bounding box --,
+    triangles [nt, 3] int32 are re-indexed and the collapsed ones dropped.  normals [nv, 3] fp32 are required.
+
+    Returns (vertices' [nv', 3], triangles' [nt', 3] int32, normals' [nv', 3]: the normalised sum of the members' normals,
+    counts' [nv'] int32: members per vertex, (n_dropped_invalid, n_collapsed)): a dropped triangle is counted once, by the first
+    that applies of invalid (an id out of range or a vertex with a non-finite coordinate) and collapsed (two corners in one
+    cell).  Vertices come in the order of their cells (x slowest), kept triangles in their original order; duplicate triangles
+    are not removed.  jt_simplify_keys, a stable sort and a scan, ONE host read (the cluster count), jt_simplify_clusters,
+    jt_simplify_triangles, two cumsums, ONE host read (the two sizes and the two counts), jt_mesh_filter_emit.  No atomics: two
+    calls return the same bits.  Eager only (the host reads size the outputs).  Empty results are [0, 3] tensors."""
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or triangles.dim() != 2 or triangles.shape[1] != 3:
+        raise ValueError("simplify_mesh: vertices are [nv, 3] and triangles [nt, 3] (got %s, %s)" % (tuple(vertices.shape), tuple(triangles.shape)))
+    if triangles.dtype != torch.int32:
+        raise ValueError("simplify_mesh: triangles are int32 vertex ids (got %s)" % triangles.dtype)
+    nv, nt = vertices.shape[0], triangles.shape[0]
+    if normals is None or tuple(normals.shape) != (nv, 3):
+        raise ValueError("simplify_mesh: one normal per vertex, [nv, 3] (got %s for %d vertices)"
+                         % (None if normals is None else tuple(normals.shape), nv))
+    lo = [float(v) for v in (lo.tolist() if torch.is_tensor(lo) else lo)]
+    hi = [float(v) for v in (hi.tolist() if torch.is_tensor(hi) else hi)]
+    if len(lo) != 3 or len(hi) != 3:
+        raise ValueError("simplify_mesh: lo and hi are three floats each")
+    cells = simplify_cells(cells)
+    regular = float(regular)
+    if not (regular > 0 and math.isfinite(regular)):
+        raise ValueError("simplify_mesh: regular is a positive finite number (got %r)" % (regular,))
+    dev = vertices.device
+    vertices = vertices.detach().contiguous().float()
+    normals = normals.detach().contiguous().float()
+    triangles = triangles.detach().contiguous()
+
+    def empty(counts):
+        return (vertices.new_empty(0, 3), triangles.new_empty(0, 3), normals.new_empty(0, 3),
+                torch.empty(0, device=dev, dtype=torch.int32), counts)
+    if nv == 0 or nt == 0:
+        return empty((0, 0))
+    keys = simplify_keys(vertices, lo, hi, cells)
+    order, head, cid, valid, totals = simplify_segments(keys, cells[0] * cells[1] * cells[2])
+    nc, n_valid = (int(v) for v in totals.tolist())
+    if nc == 0:
+        return empty((nt, 0))          # every vertex is non-finite: every triangle is invalid
+    seg_start, cluster = simplify_index(order, head, cid, valid, nc, n_valid)
+    c_pos, c_nrm, c_cnt = simplify_clusters(vertices, normals, order, seg_start, regular)
+    tri, keep, cause, used = simplify_triangles(triangles, cluster, nc)
+    out = simplify_compact(c_pos, c_nrm, c_cnt, tri, keep, cause, used)
+    return empty(out[4]) if out[1] is None else out
+
+
+def simplify_index(order, head, cid, valid, nc, n_valid):
+    """what the two kernels index with, from simplify_segments' scan and its two totals: (seg_start [nc + 1] int64: where the
+    clusters begin in `order`, and the number of valid vertices; cluster [n] int32: the cluster of every vertex, -1 for none)"""
+    pos = torch.arange(order.shape[0], device=order.device, dtype=torch.int64)
+    seg_start = torch.cat([_masked_rows(pos, head, cid, nc), pos.new_tensor([n_valid])])
+    cluster = torch.empty(order.shape[0], device=order.device, dtype=torch.int32)
+    cluster[order] = torch.where(valid, cid, torch.full_like(cid, -1)).to(torch.int32)
+    return seg_start, cluster
+
+
+def simplify_clusters(vertices, normals, order, seg_start, regular=SIMPLIFY_REGULAR):
+    """jt_simplify_clusters, one launch: (positions [nc, 3] fp32, normals [nc, 3] fp32, counts [nc] int32) of the clusters"""
+    nc, dev = seg_start.shape[0] - 1, vertices.device
+    c_pos = torch.empty(nc, 3, device=dev, dtype=torch.float32)
+    c_nrm = torch.empty(nc, 3, device=dev, dtype=torch.float32)
+    c_cnt = torch.empty(nc, device=dev, dtype=torch.int32)
+    check(lib.jt_simplify_clusters(ptr(vertices), ptr(normals), vertices.shape[0], ptr(order), ptr(seg_start), nc, float(regular),
+                                   ptr(c_pos), ptr(c_nrm), ptr(c_cnt), _stream()), "jt_simplify_clusters")
+    return c_pos, c_nrm, c_cnt
+
+
+def simplify_triangles(triangles, cluster, nc):
+    """jt_simplify_triangles, one launch: (triangles in cluster ids [nt, 3] int32, keep [nt] uint8, cause [nt] uint8: 0 kept, 1
+    invalid, 2 collapsed, used [nc] uint8)"""
+    nt, dev = triangles.shape[0], triangles.device
+    tri = torch.empty_like(triangles)
+    keep = torch.empty(nt, device=dev, dtype=torch.uint8)
+    cause = torch.empty(nt, device=dev, dtype=torch.uint8)
+    used = torch.zeros(nc, device=dev, dtype=torch.uint8)
+    check(lib.jt_simplify_triangles(ptr(triangles), nt, ptr(cluster), cluster.shape[0], nc, ptr(tri), ptr(keep), ptr(cause),
+                                    ptr(used), _stream()), "jt_simplify_triangles")
+    return tri, keep, cause, used
+
+
+def simplify_compact(c_pos, c_nrm, c_cnt, tri, keep, cause, used):
+    """the compaction behind jt_simplify_triangles: two cumsums, ONE host read (the two sizes and the two counts),
+    jt_mesh_filter_emit: (vertices', triangles', normals', counts', (n_dropped_invalid, n_collapsed)); the four arrays are None
+    when no triangle is kept"""
+    nc, nt, dev = c_pos.shape[0], tri.shape[0], c_pos.device
+    vert_end = torch.cumsum(used, 0, dtype=torch.int64)
+    tri_end = torch.cumsum(keep, 0, dtype=torch.int64)
+    nv_out, nt_out, n_invalid, n_collapsed = (int(v) for v in torch.stack([vert_end[-1], tri_end[-1], (cause == 1).sum(),
+                                                                           (cause == 2).sum()]).tolist())
+    if nt_out == 0:
+        return None, None, None, None, (n_invalid, n_collapsed)
+    vert_offset, tri_offset = vert_end.sub_(used), tri_end.sub_(keep)
+    v_out = torch.empty(nv_out, 3, device=dev, dtype=torch.float32)
+    n_out = torch.empty(nv_out, 3, device=dev, dtype=torch.float32)
+    t_out = torch.empty(nt_out, 3, device=dev, dtype=torch.int32)
+    check(lib.jt_mesh_filter_emit(ptr(c_pos), ptr(c_nrm), None, nc, ptr(tri), nt, ptr(keep), ptr(used), ptr(vert_offset),
+                                  ptr(tri_offset), nv_out, nt_out, ptr(v_out), ptr(n_out), None, ptr(t_out), _stream()),
+          "jt_mesh_filter_emit")
+    return v_out, t_out, n_out, _masked_rows(c_cnt, used.bool(), vert_offset, nv_out), (n_invalid, n_collapsed)
+
+
 # points per edge of the tile a workgroup of the component sweep owns (include/jt_render.h: JT_COMPONENTS_TILE)
 COMPONENTS_TILE = 8
 # Sweeps after which lattice_components gives up.  Measured with pointer jumping (profiles/mesh_surface_export.txt): the two

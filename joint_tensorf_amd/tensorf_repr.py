@@ -20,9 +20,10 @@ VEC_MODE = ops.VEC_MODE
 
 # what extract_mesh returns: the arrays on the device, and the lattice they were taken on (box, points per axis, iso-level)
 # normals / colors: [nv, 3] fp32 per vertex when asked for; n_components: (kept, dropped) when a component filter ran;
-# n_degenerate_normals: vertices whose density gradient was zero or non-finite (their normal is (0, 0, 0)) when normals were formed
-Mesh = collections.namedtuple("Mesh", "vertices triangles lo hi shape level normals colors n_components n_degenerate_normals",
-                              defaults=(None, None, None, None))
+# n_degenerate_normals: vertices whose density gradient was zero or non-finite (their normal is (0, 0, 0)) when normals were formed;
+# simplified: (cells, n_vertices_in, n_triangles_in, n_dropped_invalid, n_collapsed) when the mesh went through ops.simplify_mesh
+Mesh = collections.namedtuple("Mesh", "vertices triangles lo hi shape level normals colors n_components n_degenerate_normals "
+                              "simplified", defaults=(None, None, None, None, None))
 
 
 def _channel_last_param(t):
@@ -394,7 +395,7 @@ class BAT_VMSplit(torch.nn.Module):
 
     @torch.no_grad()
     def extract_mesh(self, res=None, level=0.005, cap=True, slab_points=1 << 24, keep_largest=None, min_points=None,
-                     normals=False, colors=False, view_pe_progress=None, fea_pe_progress=None):
+                     normals=False, colors=False, view_pe_progress=None, fea_pe_progress=None, simplify=None):
         """The surface {one-step opacity = level} of the field as a triangle mesh, extracted on the device (ops.mesh_from_lattice):
         a Mesh of vertices [nv, 3] fp32 in the scene box's coordinates, triangles [nt, 3] int32 with normals pointing out of the
         opaque side, and the box (lo, hi), the size (shape) and the level of the lattice the surface was taken on.  What the
@@ -408,7 +409,17 @@ class BAT_VMSplit(torch.nn.Module):
         lattice (before the cap: its zeros join nothing) with fill = 0; Mesh.n_components = (kept, dropped).
         normals: Mesh.normals = point_normals(vertices), Mesh.n_degenerate_normals the zero ones.  colors: Mesh.colors =
         point_colors(vertices, -normal): the surface seen head-on ((0, 0, -1) where the normal is zero); the normals are then
-        computed whether asked for or not, and returned only if asked for."""
+        computed whether asked for or not, and returned only if asked for.
+        simplify: K >= 1, the edge of a cell in lattice spacings -- the mesh goes through ops.simplify_mesh (vertex clustering,
+        csrc/jt_simplify.hip) with ceil((shape - 1) / K) cells per axis over the box of the lattice the surface was taken on
+        (the cap included): extraction, point_normals (computed whether asked for or not), the simplification, and only then
+        point_colors on the SIMPLIFIED vertices against their new normals -- what the field says at the representative, not an
+        average, and fewer points to shade.  Mesh.normals are then the clusters' (the normalised sum of their members'),
+        n_degenerate_normals the zero ones among them, and Mesh.simplified = (cells, n_vertices_in, n_triangles_in,
+        n_dropped_invalid, n_collapsed).  None launches nothing new."""
+        if simplify is not None:
+            if isinstance(simplify, bool) or not isinstance(simplify, (int, float)) or not (math.isfinite(simplify) and simplify >= 1):
+                raise ValueError("extract_mesh: simplify is None or a finite number >= 1, in lattice spacings (got %r)" % (simplify,))
         vol = self.dense_alpha_lattice(res, slab_points)
         lo, hi = self.aabb[0].tolist(), self.aabb[1].tolist()
         n_components = None
@@ -418,15 +429,22 @@ class BAT_VMSplit(torch.nn.Module):
         if cap:
             vol, lo, hi = ops.cap_lattice(vol, lo, hi)
         vertices, triangles = ops.mesh_from_lattice(vol, level, lo, hi)
-        nrm = col = n_bad = None
-        if normals or colors:
+        nrm = col = n_bad = simplified = None
+        if normals or colors or simplify is not None:
             nrm, n_bad = self.point_normals(vertices)
+        if simplify is not None:
+            cells = [int(math.ceil((n - 1) / float(simplify))) for n in vol.shape]
+            n_in = (int(vertices.shape[0]), int(triangles.shape[0]))
+            vertices, triangles, nrm, _, dropped = ops.simplify_mesh(vertices, triangles, nrm, lo, hi, cells)
+            simplified = (tuple(cells),) + n_in + tuple(dropped)
+            if normals:
+                n_bad = int((nrm == 0).all(-1).sum())
         if colors:
             zero = (nrm == 0).all(-1, keepdim=True)
             col = self.point_colors(vertices, torch.where(zero, nrm.new_tensor([0.0, 0.0, -1.0]), -nrm), view_pe_progress,
                                     fea_pe_progress)
         return Mesh(vertices, triangles, tuple(lo), tuple(hi), tuple(vol.shape), float(level), nrm if normals else None, col,
-                    n_components, n_bad if normals else None)
+                    n_components, n_bad if normals else None, simplified)
 
     @torch.no_grad()
     def updateAlphaMask(self, gridSize=(200, 200, 200)):
