@@ -44,7 +44,7 @@ extern "C" {
  * jt_raster_project / jt_raster_draw / jt_raster_resolve, JT_RASTER_*; 1211: + jt_mesh_unwarp_ndc / jt_mesh_filter_count / jt_mesh_filter_emit,
  * JT_UNWARP_*; 1212: + jt_simplify_keys / jt_simplify_clusters / jt_simplify_triangles, JT_SIMPLIFY_*.  Additions bump the last two
  * digits, anything a caller built against the old header would get wrong bumps the hundreds). */
-#define JT_VERSION 1212
+#define JT_VERSION 1213
 
 #define JT_OK 0
 #define JT_ERR_ARG 1         /* null pointer / bad size */
@@ -779,6 +779,54 @@ int jt_raster_draw(const float* screen, int n_vertices, const int32_t* triangles
 int jt_raster_resolve(const uint64_t* zbuf, const float* screen, int n_vertices, const int32_t* triangles, long n_triangles,
                       int n_views, int H, int W, const float* attrs, int n_attrs, const float* background, int32_t* tri,
                       float* depth, float* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Texture atlas (csrc/jt_texture.hip, and jt_raster_resolve_texture in csrc/jt_raster.hip): colour decoupled from the vertex
+ * count.  The atlas is a grid of square blocks of S x S texels (S from 4 to 64), `cols` blocks to a row, block b at column
+ * b % cols and row b / cols; every block holds the charts of the two triangles 2b and 2b + 1, right-isosceles with legs of
+ * L = S - 3 texels.  Texel (i, j) of a block -- column and row, 0 .. S - 1, centre at (i + 0.5, j + 0.5) -- belongs to triangle
+ * 2b (the lower chart, chart coordinates (i, j)) when i + j <= S - 1 and to triangle 2b + 1 (the upper chart, the lower one
+ * turned by 180 degrees: chart coordinates (S - 1 - i, S - 1 - j)) otherwise.  At chart coordinates (i, j) the barycentric weights
+ * are a = i / L for vertex 1, b = j / L for vertex 2 and 1 - a - b for vertex 0: vertex 0 sits on texel (0, 0), vertex 1 on (L, 0),
+ * vertex 2 on (0, L), and the texels beyond the hypotenuse (down to -2 / L for vertex 0) are extrapolated, not left empty.  A
+ * bilinear sample at a point of a chart then reads only texels of chart coordinates i + j <= S - 2: never the other triangle's,
+ * never another block's.  Texel (i, j) of block b is entry e = b S S + j S + i; atlas [H_atlas][W_atlas][3] uint8 with W_atlas =
+ * cols S and H_atlas = rows S holds entry e at pixel (column (b % cols) S + i, row (b / cols) S + j).
+ *
+ *   jt_texture_texels: for the entries [start, start + count) -- any range, not aligned to blocks; slabs compose to the bits of
+ *     one call -- where the appearance branch is to be asked: xyz [count][3], dirs [count][3] fp32 and valid [count] uint8, from
+ *     vertices [n_vertices][3], normals [n_vertices][3] fp32 and triangles [n_triangles][3] int32.  With (v0, v1, v2) the
+ *     triangle's vertices and a = float(i) / float(L), b = float(j) / float(L) at the entry's chart coordinates, in fp32, every
+ *     operation rounded on its own (no contraction), per axis:
+ *       p = (v0 + a (v1 - v0)) + b (v2 - v0),      m = (n0 + a (n1 - n0)) + b (n2 - n0)      the same way from the normals;
+ *       dir = fp32(double(-m) / sqrt((m_x m_x + m_y m_y) + m_z m_z)) per axis, the square root and its argument in fp64;
+ *       dir = (0, 0, -1) when that length is zero or not finite.
+ *     An entry whose triangle id is >= n_triangles (the empty upper half of the last block of an odd count) or whose triangle
+ *     names a vertex outside [0, n_vertices) is invalid: valid = 0, xyz = (0, 0, 0), dir = (0, 0, -1); nothing is read out of
+ *     bounds.  `cols` only has to describe an atlas within the limits below.
+ *   jt_texture_pack: rgb [count][3] fp32 and valid [count] of the same entry range into atlas, which the caller has zeroed:
+ *     floor(255 c + 0.5) in fp64 clamped to 0 .. 255, 0 for a NaN; an invalid entry writes nothing.  Distinct entries write
+ *     distinct bytes: no atomics, the same bits on every run.
+ *   jt_raster_resolve_texture: jt_raster_resolve with the atlas in place of vertex attributes.  tri and depth are the bits
+ *     jt_raster_resolve writes; out [n_views][H][W][3] fp32 is, at a pixel whose winner is t, the bilinear sample of chart t & 1 of
+ *     block t >> 1 at (s, u) = (l1 L, l2 L), l the perspective-correct weights of jt_raster_resolve: i0 = min(max(int(floorf(s)),
+ *     0), S - 2), fx = s - i0 (j0, fy likewise from u), the four texels (i0 + di, j0 + dj) in chart coordinates fetched as
+ *     float(byte) / 255.f, out = lerp(lerp(c00, c10, fx), lerp(c01, c11, fx), fy) with lerp(p, q, f) = fmaf(f, q - p, p) -- a
+ *     constant texture comes back exactly; background [3] (a HOST pointer) where nothing was drawn.
+ * One launch each on `stream`, nothing else; every argument is checked before the launch.  JT_ERR_ARG for a NULL pointer, a size
+ * or count below 1, a negative start, an entry range beyond the atlas, W_atlas != cols S, H_atlas no multiple of S, or an atlas
+ * of fewer charts than triangles; JT_ERR_UNSUPPORTED for S outside 4 .. 64, an atlas side beyond 16384, ceil(n_triangles / 2) S S,
+ * n_vertices or 3 n_triangles reaching 2^31, and what jt_raster_resolve refuses. */
+#define JT_TEXTURE_MIN_BLOCK 4
+#define JT_TEXTURE_MAX_BLOCK 64
+#define JT_TEXTURE_MAX_SIDE 16384
+int jt_texture_texels(const float* vertices, const float* normals, long n_vertices, const int32_t* triangles, long n_triangles,
+                      int S, int cols, long start, long count, float* xyz, float* dirs, uint8_t* valid, void* stream);
+int jt_texture_pack(const float* rgb, const uint8_t* valid, int S, int cols, long start, long count, uint8_t* atlas, int H_atlas,
+                    int W_atlas, void* stream);
+int jt_raster_resolve_texture(const uint64_t* zbuf, const float* screen, int n_vertices, const int32_t* triangles,
+                              long n_triangles, int n_views, int H, int W, const uint8_t* atlas, int S, int cols, int H_atlas,
+                              int W_atlas, const float* background, int32_t* tri, float* depth, float* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -248,6 +248,76 @@ __global__ __launch_bounds__(kRasterThreads) void k_raster_resolve(const unsigne
   }
 }
 
+// one texel of the atlas as a colour in [0, 1]
+struct RasterRgb {
+  float c[3];
+};
+
+__device__ inline RasterRgb raster_texel(const uint8_t* __restrict__ atlas, int Wa, int x, int y) {
+  const uint8_t* __restrict__ t = atlas + 3 * ((size_t)y * Wa + x);
+  return RasterRgb{{__fdiv_rn((float)t[0], 255.f), __fdiv_rn((float)t[1], 255.f), __fdiv_rn((float)t[2], 255.f)}};
+}
+
+// k_raster_resolve<true> with a per-triangle texture atlas (csrc/jt_texture.hip) in place of vertex attributes: the same winner,
+// depth and weights l1, l2; the colour is the bilinear sample of the winner's chart at chart coordinates (l1 L, l2 L), its four
+// texels clamped into the block -- the upper chart of a block (odd triangles) is the lower one turned by 180 degrees.
+__global__ __launch_bounds__(kRasterThreads) void k_raster_resolve_texture(const unsigned long long* __restrict__ zbuf,
+                                                                           const float4* __restrict__ screen, int nv,
+                                                                           const int32_t* __restrict__ triangles, int nt,
+                                                                           long pixels, int W, const uint8_t* __restrict__ atlas,
+                                                                           int S, int cols, int Wa, RasterRgb bg,
+                                                                           int32_t* __restrict__ tri_out, float* __restrict__ depth,
+                                                                           float* __restrict__ out) {
+  const long p = (long)blockIdx.x * kRasterThreads + threadIdx.x;
+  if (p >= pixels) return;
+  const int view = blockIdx.y;
+  const size_t at = (size_t)view * pixels + p;
+  const unsigned long long key = zbuf[at];
+  const int tri = (int)(unsigned)(key & 0xFFFFFFFFull);
+  int i0 = -1, i1 = -1, i2 = -1;
+  bool hit = key != ~0ull && (unsigned)tri < (unsigned)nt;
+  if (hit) {
+    i0 = triangles[3 * (size_t)tri], i1 = triangles[3 * (size_t)tri + 1], i2 = triangles[3 * (size_t)tri + 2];
+    hit = (unsigned)i0 < (unsigned)nv && (unsigned)i1 < (unsigned)nv && (unsigned)i2 < (unsigned)nv;
+  }
+  if (!hit) {
+    tri_out[at] = -1;
+    depth[at] = __builtin_inff();
+    for (int c = 0; c < 3; ++c) out[at * 3 + c] = bg.c[c];
+    return;
+  }
+  tri_out[at] = tri;
+  depth[at] = 1.f / __uint_as_float(~(unsigned)(key >> 32));
+  const float4* sv = screen + (size_t)view * nv;
+  const RasterTri t = raster_setup(sv[i0], sv[i1], sv[i2], 0);
+  long b[3];
+  raster_edges(t, (int)(p % W), (int)(p / W), b);
+  const float w0 = (float)b[0] * t.q[0], w1 = (float)b[1] * t.q[1], w2 = (float)b[2] * t.q[2];
+  const float den = w0 + w1 + w2;
+  const float l1 = w1 / den, l2 = w2 / den;
+  const float L = (float)(S - 3);
+  const float s = l1 * L, u = l2 * L;
+  const int ci = min(max((int)floorf(s), 0), S - 2), cj = min(max((int)floorf(u), 0), S - 2);
+  const float fx = s - (float)ci, fy = u - (float)cj;
+  const int block = tri >> 1;
+  const int x0 = (block % cols) * S, y0 = (block / cols) * S;      // (the entry point has checked that block lies in the atlas)
+  const bool upper = tri & 1;
+  RasterRgb c[2][2];
+#pragma unroll
+  for (int dj = 0; dj < 2; ++dj)
+#pragma unroll
+    for (int di = 0; di < 2; ++di) {
+      const int i = ci + di, j = cj + dj;
+      c[dj][di] = raster_texel(atlas, Wa, x0 + (upper ? S - 1 - i : i), y0 + (upper ? S - 1 - j : j));
+    }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float top = fmaf(fx, c[0][1].c[k] - c[0][0].c[k], c[0][0].c[k]);
+    const float bot = fmaf(fx, c[1][1].c[k] - c[1][0].c[k], c[1][0].c[k]);
+    out[at * 3 + k] = fmaf(fy, bot - top, top);
+  }
+}
+
 // what all three entry points share: the image and batch sizes
 static int raster_shape(int n_vertices, int n_views, int H, int W) {
   if (n_vertices < 1 || n_views < 1 || H < 1 || W < 1) return JT_ERR_ARG;
@@ -300,6 +370,29 @@ extern "C" int jt_raster_resolve(const uint64_t* zbuf, const float* screen, int 
     hipLaunchKernelGGL(k_raster_resolve<false>, grid, dim3(kRasterThreads), 0, (hipStream_t)stream,
                        (const unsigned long long*)zbuf, (const float4*)screen, n_vertices, triangles, (int)n_triangles, pixels, W,
                        attrs, n_attrs, bg, tri, depth, out);
+  JT_LAUNCH_CHECK();
+  return JT_OK;
+}
+
+extern "C" int jt_raster_resolve_texture(const uint64_t* zbuf, const float* screen, int n_vertices, const int32_t* triangles,
+                                         long n_triangles, int n_views, int H, int W, const uint8_t* atlas, int S, int cols,
+                                         int H_atlas, int W_atlas, const float* background, int32_t* tri, float* depth, float* out,
+                                         void* stream) {
+  if (!zbuf || !screen || !triangles || !atlas || !background || !tri || !depth || !out || n_triangles < 1) return JT_ERR_ARG;
+  if (cols < 1 || H_atlas < 1 || W_atlas < 1) return JT_ERR_ARG;
+  if (const int rc = raster_shape(n_vertices, n_views, H, W)) return rc;
+  if (n_triangles >= (1l << 31) || S < JT_TEXTURE_MIN_BLOCK || S > JT_TEXTURE_MAX_BLOCK || H_atlas > JT_TEXTURE_MAX_SIDE ||
+      W_atlas > JT_TEXTURE_MAX_SIDE)
+    return JT_ERR_UNSUPPORTED;
+  // the atlas is cols x (H_atlas / S) whole blocks and holds a chart for every triangle: no texel outside it is ever named
+  if (W_atlas != (long)cols * S || H_atlas % S != 0 || 2l * (H_atlas / S) * cols < n_triangles) return JT_ERR_ARG;
+  RasterRgb bg;
+  for (int c = 0; c < 3; ++c) bg.c[c] = background[c];
+  const long pixels = (long)H * W;
+  const dim3 grid((unsigned)((pixels + kRasterThreads - 1) / kRasterThreads), (unsigned)n_views);
+  hipLaunchKernelGGL(k_raster_resolve_texture, grid, dim3(kRasterThreads), 0, (hipStream_t)stream, (const unsigned long long*)zbuf,
+                     (const float4*)screen, n_vertices, triangles, (int)n_triangles, pixels, W, atlas, S, cols, W_atlas, bg, tri,
+                     depth, out);
   JT_LAUNCH_CHECK();
   return JT_OK;
 }

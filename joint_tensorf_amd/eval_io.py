@@ -46,6 +46,19 @@ def save_png(img, path):
     return True
 
 
+def save_png_bytes(img, path):
+    """[H, W, 3] uint8 (a tensor or an array) -> RGB, byte for byte: what a texture atlas is written with.  Returns False when PIL
+    is missing."""
+    Image = _pil()
+    if Image is None:
+        return False
+    a = img.detach().cpu().numpy() if torch.is_tensor(img) else img
+    if a.dtype.name != "uint8" or a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError("save_png_bytes: uint8 [H, W, 3], got %s %s" % (a.dtype, a.shape))
+    Image.fromarray(a).save(path)
+    return True
+
+
 def write_quant_pose(output_path, R_error, t_error):
     """quant_pose.txt: `i err_R err_t` per training view (model/bat.py:255-259)"""
     with open(os.path.join(output_path, "quant_pose.txt"), "w") as f:

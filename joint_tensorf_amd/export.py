@@ -17,7 +17,7 @@ points, stay.  `--surface.normals=true` writes per-vertex normals (the normalise
 
 `--preview.views=N|all` looks at the result: the mesh drawn from N training cameras of cameras.json (evenly spaced over the set)
 by the device rasteriser (csrc/jt_raster.hip), OUT/preview/mesh_<idx>.png, at `--preview.size=[H,W]` (default
-data.image_size), shaded by `--preview.shade=color|normal|depth`; `--preview.cull=true` drops back faces.
+data.image_size), shaded by `--preview.shade=color|normal|depth|texture`; `--preview.cull=true` drops back faces.
 `--preview.check=true` also renders the field at the same cameras (OUT/preview/field_<idx>.png) and writes OUT/report.json:
 per view the coverage of mesh and field, their IoU, the median depth difference, the PSNR of the colours and what became of
 every triangle.  It reports; it judges nothing.  The preview needs the run's image set and a world-space scene (not
@@ -41,6 +41,19 @@ mesh.ply gains the comment `simplify cell K cells CX CY CZ from NV NT collapsed 
 `--preview.*` / `--preview.check` draw and score the simplified mesh.  Without a `--simplify.*` option mesh.ply is what it was,
 byte for byte.
 
+`--texture.block=S` (an integer from 4 to 64) exports a TEXTURED mesh: a per-triangle texture atlas baked on the device from
+the field (TensorVMSplit.bake_texture; csrc/jt_texture.hip) -- square blocks of S x S texels, two right-isosceles charts of legs
+S - 3 texels per block, every texel the appearance branch at its point of the flat triangle seen against the interpolated
+normal -- so colour resolution no longer depends on the vertex count, which `--simplify.cell` cuts.  It is baked last, on the
+mesh as it is written (after `--surface.keep_largest` / `min_points` and `--simplify.cell`), in the frame the field lives in.
+OUT gains atlas.png (RGB), mesh.obj + mesh.mtl (`map_Kd atlas.png`; what Blender reads), and mesh.ply carries per-face texture
+coordinates (`property list uchar float texcoord`, `comment TextureFile atlas.png`: what MeshLab, CloudCompare, Open3D and
+trimesh read) and the comment `texture block S atlas W H`; report.json repeats the numbers.  `--preview.shade=texture` draws
+the mesh with its atlas (jt_raster_resolve_texture); with `--preview.check=true` report.json's psnr_color scores the textured
+draw and psnr_vertex_color the same cameras drawn with vertex colours.  Together with `--frame.space=world` on a camera.ndc
+scene it is refused: a chart that is linear in NDC is not linear in world space (perspective-correct charts are not built).
+Without a `--texture.*` option the export writes what it wrote, byte for byte.
+
 Every other `--key.sub=value` is one of the dotted overrides of joint_tensorf_amd.train."""
 import sys
 
@@ -53,7 +66,7 @@ SURFACE_DEFAULTS = dict(keep_largest=None, min_points=None, normals=False, color
 # pictures of the mesh from the training cameras (views: how many, 0 = none, or "all"; size: [H, W], None = data.image_size;
 # shade: what a pixel shows), back faces culled or not, and the check against the volume render of the same cameras
 PREVIEW_DEFAULTS = dict(views=0, size=None, shade="color", check=False, cull=False)
-PREVIEW_SHADES = ("color", "normal", "depth")
+PREVIEW_SHADES = ("color", "normal", "depth", "texture")
 PREVIEW_MAX_SIZE = 16384        # what the rasteriser draws (include/jt_render.h)
 # the coordinates mesh.ply is written in (space: "world" or "ndc"; None = what the scene lives in: ndc for camera.ndc, world
 # otherwise) and, for an NDC scene exported to world, the depth along the reference axis beyond which geometry is dropped
@@ -61,6 +74,8 @@ FRAME_DEFAULTS = dict(space=None, max_depth=None)
 FRAME_SPACES = ("world", "ndc")
 # the simplification of the extracted mesh by vertex clustering (cell: the edge of a cell in lattice spacings, None = off)
 SIMPLIFY_DEFAULTS = dict(cell=None)
+# the texture atlas baked for the mesh (block: the edge of a block of two charts in texels, an integer from 4 to 64; None = off)
+TEXTURE_DEFAULTS = dict(block=None)
 
 
 def _option_group(over, name, defaults):
@@ -85,19 +100,22 @@ def build_options(argv):
         raise SystemExit("usage: python -m joint_tensorf_amd.export --yaml=NAME --load=CKPT --output_path=OUT [--mesh.res=N] "
                          "[--mesh.level=L] [--mesh.cap=true|false] [--surface.keep_largest=K] [--surface.min_points=M] "
                          "[--surface.normals=true|false] [--surface.colors=true|false] [--preview.views=N|all] [--preview.size=[H,W]] "
-                         "[--preview.shade=color|normal|depth] [--preview.check=true|false] [--preview.cull=true|false] "
-                         "[--frame.space=world|ndc] [--frame.max_depth=D] [--simplify.cell=K] "
+                         "[--preview.shade=color|normal|depth|texture] [--preview.check=true|false] [--preview.cull=true|false] "
+                         "[--frame.space=world|ndc] [--frame.max_depth=D] [--simplify.cell=K] [--texture.block=S] "
                          "[--data.root=DIR --key.sub=value ...]")
     mesh = _option_group(over, "mesh", MESH_DEFAULTS)
     surface = _option_group(over, "surface", SURFACE_DEFAULTS)
     preview = _option_group(over, "preview", PREVIEW_DEFAULTS)
     frame = _option_group(over, "frame", FRAME_DEFAULTS)
     simplify = _option_group(over, "simplify", SIMPLIFY_DEFAULTS)
+    texture = _option_group(over, "texture", TEXTURE_DEFAULTS)
     opt = apply_overrides(load_options(name), over)
     opt.mesh, opt.surface, opt.preview, opt.frame, opt.simplify = mesh, surface, preview, frame, simplify
+    opt.texture = texture
     _check_preview(preview)
     _check_simplify(simplify)
     _check_frame(frame, bool(opt.camera.ndc))
+    _check_texture(texture, preview, frame, bool(opt.camera.ndc))
     for k in ("keep_largest", "min_points"):
         v = surface[k]
         if v is not None:
@@ -168,6 +186,23 @@ def _check_simplify(simplify):
         if isinstance(k, bool) or not isinstance(k, (int, float)) or not math.isfinite(k) or not k >= 1:
             raise SystemExit("--simplify.cell is a finite number of at least 1, the edge of a cell in lattice spacings (got %r)" % (k,))
         simplify.cell = float(k)
+
+
+def _check_texture(texture, preview, frame, ndc):
+    from . import mesh_io
+    s = texture.block
+    if s is not None:
+        if (isinstance(s, bool) or not isinstance(s, (int, float)) or float(s) != int(s)
+                or not mesh_io.TEXTURE_MIN_BLOCK <= int(s) <= mesh_io.TEXTURE_MAX_BLOCK):
+            raise SystemExit("--texture.block is an integer from %d to %d, the edge in texels of a block of two charts (got %r)"
+                             % (mesh_io.TEXTURE_MIN_BLOCK, mesh_io.TEXTURE_MAX_BLOCK, s))
+        texture.block = int(s)
+        if ndc and frame.space == "world":
+            raise SystemExit("--texture.block together with --frame.space=world is not available: the atlas is baked in NDC, where "
+                             "the field lives, and a chart that is linear in NDC is not linear in world space (perspective-correct "
+                             "charts are not built); export the textured mesh in NDC, or the world-space mesh with --surface.colors")
+    elif preview.shade == "texture":
+        raise SystemExit("--preview.shade=texture draws the mesh with its texture atlas: name the block size with --texture.block=S")
 
 
 def unwarps(opt):

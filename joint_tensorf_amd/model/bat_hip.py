@@ -1088,10 +1088,21 @@ class Model(torch.nn.Module):
         lives in -- NDC for a camera.ndc scene, where the cells are perspective-sized, before unwarp_mesh carries it out; normals
         are then the clusters', colours evaluated at the simplified vertices.  The PLY gains the comment `simplify cell K cells
         CX CY CZ from NV NT collapsed C` and the result `simplified` = (cells, n_vertices_in, n_triangles_in,
-        n_dropped_invalid, n_collapsed), which preview_scene's report.json repeats."""
-        from .. import mesh_io
+        n_dropped_invalid, n_collapsed), which preview_scene's report.json repeats.
+
+        opt.texture.block = S (an integer from 4 to 64; absent or None: off) bakes a per-triangle texture atlas on the device
+        (extract_mesh(texture=S) -> bake_texture, csrc/jt_texture.hip), last, on the mesh as it is written and in the frame the
+        field lives in: <directory>/atlas.png (RGB), mesh.ply with per-face texture coordinates, `comment TextureFile atlas.png`
+        and the comment `texture block S atlas W H`, and mesh.obj + mesh.mtl (mesh_io.write_obj).  The result gains `texture` =
+        Opt(block, width, height, atlas, obj, mtl), which report.json repeats.  Not together with frame.space = world on a
+        camera.ndc scene (a chart that is linear in NDC is not linear in world space): a ValueError before any work."""
+        from .. import eval_io, mesh_io
         mcfg = opt.get("mesh", None) or {}
         unwarp = self.unwarps(opt)
+        block = (opt.get("texture", None) or {}).get("block", None)
+        if block is not None and unwarp:
+            raise ValueError("export_scene: texture.block together with frame.space = world on a camera.ndc scene is not available "
+                             "(the atlas is baked in NDC; a chart that is linear there is not linear in world space)")
         if unwarp and self.train_data is None:
             raise ValueError("export_scene: frame.space = world on a camera.ndc scene needs the training set (its intrinsics make "
                              "the NDC map)")
@@ -1115,7 +1126,10 @@ class Model(torch.nn.Module):
         mesh = nerf.tensorf.extract_mesh(res=mcfg.get("res", None), level=float(mcfg.get("level", 0.005)),
                                          cap=bool(mcfg.get("cap", True)), keep_largest=scfg.get("keep_largest", None),
                                          min_points=scfg.get("min_points", None), normals=ext_normals, colors=ext_colors,
-                                         simplify=(opt.get("simplify", None) or {}).get("cell", None), **pe)
+                                         simplify=(opt.get("simplify", None) or {}).get("cell", None), **pe,
+                                         **({} if block is None else {"texture": block}))
+        if block is not None and mesh.texture is None:
+            raise ValueError("export_scene: the mesh is empty (level %r): nothing to texture" % (mesh.level,))
         frame = None
         if unwarp:
             mesh, frame = self.unwarp_mesh(opt, mesh)
@@ -1135,8 +1149,19 @@ class Model(torch.nn.Module):
             out.unwarp = frame
             comments.append("unwarp near %r sx %r sy %r" % (frame.near, frame.sx, frame.sy))
             comments.append("dropped beyond %d far %d" % (frame.n_dropped_beyond, frame.n_dropped_far))
+        textured = {}
+        if mesh.texture is not None:
+            lay = mesh.texture.layout
+            out.texture = Opt(block=lay.block, width=lay.width, height=lay.height, atlas=os.path.join(directory, "atlas.png"),
+                              obj=os.path.join(directory, "mesh.obj"), mtl=os.path.join(directory, "mesh.mtl"))
+            comments.append("texture block %d atlas %d %d" % (lay.block, lay.width, lay.height))
+            textured = dict(texcoords=mesh.texture.uv, texture_file="atlas.png", texture_size=(lay.width, lay.height))
+            if not eval_io.save_png_bytes(mesh.texture.atlas, out.texture.atlas):
+                raise RuntimeError("export_scene: atlas.png cannot be written without PIL, and a textured mesh is nothing without it")
+            mesh_io.write_obj(out.texture.obj, mesh.vertices, mesh.triangles, mesh.texture.uv, (lay.width, lay.height),
+                              normals=mesh.normals if want_normals else None, texture_file="atlas.png")
         mesh_io.write_ply(out.mesh, mesh.vertices, mesh.triangles, comments, normals=mesh.normals if want_normals else None,
-                          colors=mesh.colors if want_colors else None)
+                          colors=mesh.colors if want_colors else None, **textured)
         if self.train_data is None:
             print("joint_tensorf_amd: export_scene without a training set: %s written, the cameras skipped" % out.mesh)
             return out
@@ -1203,13 +1228,15 @@ class Model(torch.nn.Module):
         given) drawn by the device rasteriser (ops.rasterize) from opt.preview.views training cameras, evenly spaced over the set
         ("all": every one), at opt.preview.size = [H, W] (default the image set's size; the intrinsics are rescaled), shaded by
         opt.preview.shade: `color` (the vertex colours; point_colors against the normal when the mesh carries none), `normal`
-        (0.5 n + 0.5) or `depth` (inverse depth through eval_io.normalized_invdepth); opt.preview.cull drops back faces.
+        (0.5 n + 0.5), `depth` (inverse depth through eval_io.normalized_invdepth) or `texture` (the mesh's atlas, Mesh.texture,
+        sampled by jt_raster_resolve_texture; it needs opt.texture.block); opt.preview.cull drops back faces.
 
         With opt.preview.check also preview/field_<idx>.png, the field rendered at the same cameras and size (render_by_slices,
         eval mode), and <directory>/report.json: per view coverage_mesh (share of pixels a triangle covers), coverage_field
         (opacity >= 0.5), their iou, depth_abs_median (over pixels the mesh covers and the field renders with opacity >= 0.99;
         the field's depth with the `- near + 0.05` of batBase.py:150 undone; both are distances along the camera axis),
-        psnr_color (shade color: over pixels both cover) and the five triangle counts (ops.RASTER_STATUS); then the means over
+        psnr_color (shade color or texture: over pixels both cover; shade texture adds psnr_vertex_color, the same cameras drawn
+        with vertex colours, so one report shows what the texture buys) and the five triangle counts (ops.RASTER_STATUS); then the means over
         the views.  A camera.ndc scene is drawn only as a world-space mesh (opt.frame.space == "world": a given mesh is
         unwarp_mesh's, one extracted here goes through it); its render's depth is carried to the camera axis in world units
         (eval_io.ndc_render_depth) and the report gains disparity_abs_median, the median |1/d_mesh - 1/d_field| over the same pixels.  A value over an empty set of pixels is null and left out of its mean.  Nothing is judged: the tool reports.
@@ -1228,8 +1255,12 @@ class Model(torch.nn.Module):
         nerf = self.graph.nerf
         tf = nerf.tensorf
         shade = cfg.get("shade", "color")
-        if shade not in ("color", "normal", "depth"):
-            raise ValueError("preview_scene: shade is color, normal or depth (got %r)" % (shade,))
+        if shade not in ("color", "normal", "depth", "texture"):
+            raise ValueError("preview_scene: shade is color, normal, depth or texture (got %r)" % (shade,))
+        block = (opt.get("texture", None) or {}).get("block", None)
+        if shade == "texture" and (block is None or unwarp):
+            raise ValueError("preview_scene: shade texture needs texture.block (--texture.block=S), and a scene that is not carried "
+                             "from NDC to world space")
         if mesh is None:
             mcfg, scfg = opt.get("mesh", None) or {}, opt.get("surface", None) or {}
             extra = {}
@@ -1241,9 +1272,12 @@ class Model(torch.nn.Module):
                         extra[key] = interp_schedule(nerf.progress_host, opt[name]) if _has(opt, name) else 1.0
             mesh = tf.extract_mesh(res=mcfg.get("res", None), level=float(mcfg.get("level", 0.005)), cap=bool(mcfg.get("cap", True)),
                                    keep_largest=scfg.get("keep_largest", None), min_points=scfg.get("min_points", None),
-                                   simplify=(opt.get("simplify", None) or {}).get("cell", None), **extra)
+                                   simplify=(opt.get("simplify", None) or {}).get("cell", None), **extra,
+                                   **({"texture": block} if shade == "texture" else {}))
             if unwarp:
                 mesh = self.unwarp_mesh(opt, mesh)[0]
+        if shade == "texture" and mesh.triangles.shape[0] and mesh.texture is None:
+            raise ValueError("preview_scene: shade texture needs a mesh with a texture (extract_mesh(texture=S))")
         if unwarp and ((shade in ("color", "normal") and mesh.normals is None) or (shade == "color" and mesh.colors is None)):
             raise ValueError("preview_scene: a world-space mesh of a camera.ndc scene must bring the normals / colours it is shaded "
                              "with (they are evaluated in NDC, before unwarp_mesh)")
@@ -1259,7 +1293,8 @@ class Model(torch.nn.Module):
         proj = mesh_io.projection_matrices(pose, intr, size=(H, W), image_size=(opt.H, opt.W))
         white = bool(opt.nerf.setbg_opaque)
         attrs, background = None, 0.0
-        if shade in ("color", "normal"):
+        vertex_colors = shade == "color" or (shade == "texture" and cfg.get("check", False))
+        if vertex_colors or shade == "normal":
             nrm = mesh.normals if mesh.normals is not None else tf.point_normals(mesh.vertices)[0]
             if shade == "normal":
                 attrs = 0.5 * nrm + 0.5
@@ -1273,8 +1308,18 @@ class Model(torch.nn.Module):
                 zero = (nrm == 0).all(-1, keepdim=True)
                 attrs = tf.point_colors(mesh.vertices, torch.where(zero, nrm.new_tensor([0.0, 0.0, -1.0]), -nrm), **pe)
                 background = 1.0 if white else 0.0
-        drawn = ops.rasterize(mesh.vertices, mesh.triangles, proj, H, W, attrs=attrs, cull=bool(cfg.get("cull", False)),
-                              background=background)
+        drawn_vertex = None
+        if shade == "texture":
+            # the atlas in place of the vertex colours; with the check also the vertex colours, for psnr_vertex_color
+            if attrs is not None:
+                drawn_vertex = ops.rasterize(mesh.vertices, mesh.triangles, proj, H, W, attrs=attrs, cull=bool(cfg.get("cull", False)),
+                                             background=background)
+            background = 1.0 if white else 0.0
+            drawn = ops.rasterize(mesh.vertices, mesh.triangles, proj, H, W, cull=bool(cfg.get("cull", False)), background=background,
+                                  texture=(mesh.texture.atlas, mesh.texture.layout))
+        else:
+            drawn = ops.rasterize(mesh.vertices, mesh.triangles, proj, H, W, attrs=attrs, cull=bool(cfg.get("cull", False)),
+                                  background=background)
         covered = drawn.tri >= 0
         invdepth = torch.where(covered, 1 / drawn.depth, torch.zeros_like(drawn.depth))
         path = os.path.join(directory, "preview")
@@ -1299,7 +1344,8 @@ class Model(torch.nn.Module):
         size0 = (opt.H, opt.W)
         rows = []
         counts = drawn.status_counts.tolist()
-        keys = self.PREVIEW_REPORT_KEYS + (("disparity_abs_median",) if unwarp else ())
+        keys = (self.PREVIEW_REPORT_KEYS + (("psnr_vertex_color",) if shade == "texture" else ())
+                + (("disparity_abs_median",) if unwarp else ()))
         if unwarp:
             sx, sy, ndc_near = self.ndc_frame(opt)
             pixels = torch.arange(H * W, device=pose.device)
@@ -1333,9 +1379,14 @@ class Model(torch.nn.Module):
                        "iou": float((m & f).sum() / union) if int(union) else 1.0,
                        "depth_abs_median": float((drawn.depth[j] - depth_f)[solid].abs().median()) if int(solid.sum()) else None,
                        "psnr_color": None}
-                if shade == "color" and int(both.sum()):
+                if shade in ("color", "texture") and int(both.sum()):
                     mse = ((drawn.attrs[j] - rgb)[both] ** 2).mean().clamp(min=1e-10)
                     row["psnr_color"] = float(-10 * torch.log10(mse))
+                if shade == "texture":
+                    row["psnr_vertex_color"] = None
+                    if int(both.sum()):
+                        mse = ((drawn_vertex.attrs[j] - rgb)[both] ** 2).mean().clamp(min=1e-10)
+                        row["psnr_vertex_color"] = float(-10 * torch.log10(mse))
                 if unwarp:
                     # depth differences out to infinity say little: the same pixels in inverse depth
                     row["disparity_abs_median"] = (float((1 / drawn.depth[j] - 1 / depth_f)[solid].abs().median())
@@ -1353,6 +1404,9 @@ class Model(torch.nn.Module):
                   "n_triangles": int(mesh.triangles.shape[0]), "views": rows, "mean": means}
         if mesh.simplified is not None:
             report["simplified"] = [list(mesh.simplified[0])] + [int(v) for v in mesh.simplified[1:]]
+        if mesh.texture is not None:
+            lay = mesh.texture.layout
+            report["texture"] = {"block": lay.block, "atlas": [lay.width, lay.height], "file": "atlas.png"}
         out.report = os.path.join(directory, "report.json")
         with open(out.report, "w") as fh:
             json.dump(report, fh, indent=1)
@@ -1366,6 +1420,8 @@ class Model(torch.nn.Module):
                        % (len(idx), H, W, show(means["coverage_mesh"], "%.3f"), show(means["coverage_field"], "%.3f"),
                           show(means["iou"], "%.3f"), show(means["depth_abs_median"], "%.4f"), show(means["psnr_color"], "%.2f dB"),
                           round(means["triangles"]["drawn"]), mesh.triangles.shape[0], out.report))
+        if shade == "texture":
+            out.summary += "; vertex colours alone %s" % show(means["psnr_vertex_color"], "%.2f dB")
         if unwarp:
             out.summary += "; median disparity difference %s" % show(means["disparity_abs_median"], "%.5f")
         return out

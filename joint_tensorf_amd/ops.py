@@ -1944,7 +1944,93 @@ def raster_resolve(zbuf, screen, triangles, attrs=None, background=0.0):
     return tri, depth, out
 
 
-def rasterize(vertices, triangles, proj, H, W, attrs=None, near=1e-3, cull=False, background=0.0, views_per_call=8):
+def texture_layout(n_triangles, block):
+    """mesh_io.texture_layout: the atlas of n_triangles charts in blocks of `block` texels (pure host arithmetic, no GPU)"""
+    from . import mesh_io
+    return mesh_io.texture_layout(n_triangles, block)
+
+
+def _texture_range(layout, start, count, who):
+    start, count = int(start), int(count)
+    if start < 0 or count < 1 or start + count > layout.n_entries:
+        raise ValueError("%s: entries [%d, %d) are not within the atlas' %d" % (who, start, start + count, layout.n_entries))
+    return start, count
+
+
+def texture_texels(vertices, triangles, normals, layout, start=0, count=None):
+    """jt_texture_texels, one launch: for the entries [start, start + count) of `layout` (texture_layout's; count None: to the
+    end) the points xyz [count, 3] fp32 on the triangles (vertices [nv, 3] fp32, triangles [nt, 3] int32), the directions dirs
+    [count, 3] fp32 they are looked at along (minus the interpolated normals [nv, 3], normalised; (0, 0, -1) where that is zero
+    or not finite) and valid [count] uint8 (0: the empty half of the last block, or a triangle with a vertex id out of range).
+    Any range: slabs compose to the bits of one call."""
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or triangles.dim() != 2 or triangles.shape[1] != 3:
+        raise ValueError("texture_texels: vertices are [nv, 3] and triangles [nt, 3] (got %s, %s)" % (tuple(vertices.shape), tuple(triangles.shape)))
+    if triangles.dtype != torch.int32:
+        raise ValueError("texture_texels: triangles are int32 vertex ids (got %s)" % triangles.dtype)
+    if tuple(normals.shape) != tuple(vertices.shape):
+        raise ValueError("texture_texels: one normal per vertex, [nv, 3] (got %s for %d vertices)" % (tuple(normals.shape), vertices.shape[0]))
+    if triangles.shape[0] != layout.n_triangles or vertices.shape[0] < 1:
+        raise ValueError("texture_texels: the layout is of %d triangles, the mesh has %d (and %d vertices)"
+                         % (layout.n_triangles, triangles.shape[0], vertices.shape[0]))
+    start, count = _texture_range(layout, start, layout.n_entries - int(start) if count is None else count, "texture_texels")
+    dev = vertices.device
+    vertices, normals = vertices.detach().contiguous().float(), normals.detach().contiguous().float()
+    triangles = triangles.detach().contiguous()
+    xyz = torch.empty(count, 3, device=dev, dtype=torch.float32)
+    dirs = torch.empty(count, 3, device=dev, dtype=torch.float32)
+    valid = torch.empty(count, device=dev, dtype=torch.uint8)
+    check(lib.jt_texture_texels(ptr(vertices), ptr(normals), vertices.shape[0], ptr(triangles), triangles.shape[0], layout.block,
+                                layout.cols, start, count, ptr(xyz), ptr(dirs), ptr(valid), _stream()), "jt_texture_texels")
+    return xyz, dirs, valid
+
+
+def texture_pack(rgb, valid, layout, atlas, start=0):
+    """jt_texture_pack, one launch: colours rgb [count, 3] fp32 and valid [count] uint8 of the entries [start, start + count)
+    into atlas [height, width, 3] uint8 (zeroed by the caller) as floor(255 c + 0.5) clamped to 0 .. 255, 0 for a NaN; an
+    invalid entry writes nothing.  Returns atlas."""
+    if rgb.dim() != 2 or rgb.shape[1] != 3 or tuple(valid.shape) != (rgb.shape[0],) or valid.dtype != torch.uint8:
+        raise ValueError("texture_pack: rgb is [count, 3] and valid uint8 [count] (got %s, %s %s)"
+                         % (tuple(rgb.shape), valid.dtype, tuple(valid.shape)))
+    if atlas.dtype != torch.uint8 or tuple(atlas.shape) != (layout.height, layout.width, 3) or not atlas.is_contiguous():
+        raise ValueError("texture_pack: the atlas is contiguous uint8 [%d, %d, 3] (got %s %s)"
+                         % (layout.height, layout.width, atlas.dtype, tuple(atlas.shape)))
+    start, count = _texture_range(layout, start, rgb.shape[0], "texture_pack")
+    rgb, valid = rgb.detach().contiguous().float(), valid.contiguous()
+    check(lib.jt_texture_pack(ptr(rgb), ptr(valid), layout.block, layout.cols, start, count, ptr(atlas), layout.height, layout.width,
+                              _stream()), "jt_texture_pack")
+    return atlas
+
+
+def _texture_arg(texture, n_triangles, who):
+    """(atlas, layout) of a mesh of n_triangles: a contiguous uint8 [height, width, 3] tensor and its texture_layout"""
+    atlas, layout = texture
+    if layout.n_triangles != n_triangles:
+        raise ValueError("%s: the texture's layout is of %d triangles, the mesh has %d" % (who, layout.n_triangles, n_triangles))
+    if atlas.dtype != torch.uint8 or tuple(atlas.shape) != (layout.height, layout.width, 3):
+        raise ValueError("%s: the atlas is uint8 [%d, %d, 3] (got %s %s)" % (who, layout.height, layout.width, atlas.dtype, tuple(atlas.shape)))
+    return atlas.detach().contiguous(), layout
+
+
+def raster_resolve_texture(zbuf, screen, triangles, atlas, layout, background=0.0):
+    """jt_raster_resolve_texture: (tri [V, H, W] int32, depth [V, H, W] fp32 -- the bits of raster_resolve -- and out [V, H, W, 3]
+    fp32: the atlas sampled bilinearly inside the winner's chart, `background` (a number or three) elsewhere); one launch"""
+    V, H, W = zbuf.shape
+    nv, nt = screen.shape[1], triangles.shape[0]
+    dev = zbuf.device
+    atlas, layout = _texture_arg((atlas, layout), nt, "raster_resolve_texture")
+    tri = torch.empty(V, H, W, device=dev, dtype=torch.int32)
+    depth = torch.empty(V, H, W, device=dev, dtype=torch.float32)
+    out = torch.empty(V, H, W, 3, device=dev, dtype=torch.float32)
+    bg = [float(background)] * 3 if not hasattr(background, "__len__") else [float(v) for v in background]
+    if len(bg) != 3:
+        raise ValueError("rasterize: %d background values for the 3 channels of a texture" % len(bg))
+    check(lib.jt_raster_resolve_texture(ptr(zbuf), ptr(screen), nv, ptr(triangles), nt, V, H, W, ptr(atlas), layout.block, layout.cols,
+                                        layout.height, layout.width, (ctypes.c_float * 3)(*bg), ptr(tri), ptr(depth), ptr(out),
+                                        _stream()), "jt_raster_resolve_texture")
+    return tri, depth, out
+
+
+def rasterize(vertices, triangles, proj, H, W, attrs=None, near=1e-3, cull=False, background=0.0, views_per_call=8, texture=None):
     """A triangle mesh (vertices [nv, 3] fp32, triangles [nt, 3] int32) seen through proj [V, 3, 4] -- one matrix per view that
     takes a homogeneous mesh-space point to (x w, y w, w) in pixel units, pixel centres at half-integers (mesh_io.
     projection_matrices builds it from cameras) -- at H x W (csrc/jt_raster.hip).  Returns Opt(tri [V, H, W] int32: the nearest
@@ -1954,7 +2040,11 @@ def rasterize(vertices, triangles, proj, H, W, attrs=None, near=1e-3, cull=False
 
     Per slab of `views_per_call` views: a z-buffer of 8 bytes per pixel is allocated and cleared, then jt_raster_project,
     jt_raster_draw, jt_raster_resolve.  Everything stays on the device and nothing is read back; coverage is decided in
-    integers and depth by one 64-bit atomic minimum per pixel, so two calls return the same bits however the views are batched."""
+    integers and depth by one 64-bit atomic minimum per pixel, so two calls return the same bits however the views are batched.
+
+    texture = (atlas, layout) -- a uint8 [height, width, 3] atlas and its texture_layout, TensorVMSplit.bake_texture's -- in
+    place of attrs (the two exclude each other): the resolve is jt_raster_resolve_texture and the result's attrs [V, H, W, 3]
+    the atlas sampled bilinearly inside the winner's chart.  Without it nothing changes."""
     from .options import Opt
     H, W, step = int(H), int(W), int(views_per_call)
     if vertices.dim() != 2 or vertices.shape[1] != 3 or triangles.dim() != 2 or triangles.shape[1] != 3:
@@ -1976,17 +2066,24 @@ def rasterize(vertices, triangles, proj, H, W, attrs=None, near=1e-3, cull=False
         if attrs.dim() != 2 or attrs.shape[0] != vertices.shape[0] or not 1 <= attrs.shape[1] <= RASTER_MAX_ATTRS:
             raise ValueError("rasterize: attrs are [nv, C] with 1 <= C <= %d (got %s for %d vertices)"
                              % (RASTER_MAX_ATTRS, tuple(attrs.shape), vertices.shape[0]))
+    if texture is not None:
+        if attrs is not None:
+            raise ValueError("rasterize: attrs and texture exclude each other")
+        texture = _texture_arg(texture, triangles.shape[0], "rasterize")
     codes = torch.arange(len(RASTER_STATUS), device=dev, dtype=torch.uint8)
     tri, depth, out, counts = [], [], [], []
     for v0 in range(0, proj.shape[0], step):
         screen = raster_project(vertices, proj[v0:v0 + step], near)
         zbuf, status = raster_draw(screen, triangles, H, W, cull)
-        t, d, o = raster_resolve(zbuf, screen, triangles, attrs, background)
+        if texture is not None:
+            t, d, o = raster_resolve_texture(zbuf, screen, triangles, texture[0], texture[1], background)
+        else:
+            t, d, o = raster_resolve(zbuf, screen, triangles, attrs, background)
         tri.append(t)
         depth.append(d)
         out.append(o)
         counts.append(torch.stack([(status == c).sum(1) for c in codes], 1))
-    return Opt(tri=torch.cat(tri), depth=torch.cat(depth), attrs=torch.cat(out) if attrs is not None else None,
+    return Opt(tri=torch.cat(tri), depth=torch.cat(depth), attrs=torch.cat(out) if attrs is not None or texture is not None else None,
                status_counts=torch.cat(counts))
 
 

@@ -21,9 +21,10 @@ VEC_MODE = ops.VEC_MODE
 # what extract_mesh returns: the arrays on the device, and the lattice they were taken on (box, points per axis, iso-level)
 # normals / colors: [nv, 3] fp32 per vertex when asked for; n_components: (kept, dropped) when a component filter ran;
 # n_degenerate_normals: vertices whose density gradient was zero or non-finite (their normal is (0, 0, 0)) when normals were formed;
-# simplified: (cells, n_vertices_in, n_triangles_in, n_dropped_invalid, n_collapsed) when the mesh went through ops.simplify_mesh
+# simplified: (cells, n_vertices_in, n_triangles_in, n_dropped_invalid, n_collapsed) when the mesh went through ops.simplify_mesh;
+# texture: bake_texture's Opt(atlas uint8 [H, W, 3], uv [nt, 3, 2] in pixel units, layout) when a texture was asked for
 Mesh = collections.namedtuple("Mesh", "vertices triangles lo hi shape level normals colors n_components n_degenerate_normals "
-                              "simplified", defaults=(None, None, None, None, None))
+                              "simplified texture", defaults=(None, None, None, None, None, None))
 
 
 def _channel_last_param(t):
@@ -394,8 +395,34 @@ class BAT_VMSplit(torch.nn.Module):
         return out
 
     @torch.no_grad()
+    def bake_texture(self, vertices, triangles, normals, block=8, slab_points=1 << 20, view_pe_progress=None, fea_pe_progress=None):
+        """A per-triangle texture atlas of the appearance branch for the mesh (vertices [nv, 3] fp32, triangles [nt, 3] int32,
+        normals [nv, 3] fp32), baked on the device: Opt(atlas: uint8 [H, W, 3], uv: [nt, 3, 2] fp32, the corners of every chart
+        in atlas pixel units (x right, y down; mesh_io.texture_uv), layout: ops.texture_layout(nt, block)).  Blocks of `block` x
+        `block` texels hold the charts of two triangles each (include/jt_render.h: "Texture atlas"); colour resolution is then
+        a matter of `block`, not of the vertex count.  In slabs of `slab_points` entries: ops.texture_texels (the point on the
+        flat triangle, seen against the interpolated normal; texels beyond the hypotenuse are extrapolated, so no dilation pass is
+        needed) -> point_colors (clamped to the scene box, the blur and PE state of the last forward, as for vertex colours) ->
+        ops.texture_pack.  Slabs compose to the bits of one pass."""
+        from . import mesh_io
+        from .options import Opt
+        if int(slab_points) < 1:
+            raise ValueError("bake_texture: slab_points is at least 1 (got %r)" % (slab_points,))
+        if triangles.dim() != 2 or triangles.shape[1] != 3 or triangles.shape[0] < 1:
+            raise ValueError("bake_texture: triangles are [nt, 3] with nt >= 1 (got %s): an empty mesh has nothing to texture"
+                             % (tuple(triangles.shape),))
+        layout = ops.texture_layout(int(triangles.shape[0]), block)
+        atlas = torch.zeros(layout.height, layout.width, 3, device=vertices.device, dtype=torch.uint8)
+        for start in range(0, layout.n_entries, int(slab_points)):
+            count = min(int(slab_points), layout.n_entries - start)
+            xyz, dirs, valid = ops.texture_texels(vertices, triangles, normals, layout, start, count)
+            rgb = self.point_colors(xyz, dirs, view_pe_progress, fea_pe_progress, slab_points=slab_points)
+            ops.texture_pack(rgb, valid, layout, atlas, start)
+        return Opt(atlas=atlas, uv=torch.from_numpy(mesh_io.texture_uv(layout)).to(vertices.device), layout=layout)
+
+    @torch.no_grad()
     def extract_mesh(self, res=None, level=0.005, cap=True, slab_points=1 << 24, keep_largest=None, min_points=None,
-                     normals=False, colors=False, view_pe_progress=None, fea_pe_progress=None, simplify=None):
+                     normals=False, colors=False, view_pe_progress=None, fea_pe_progress=None, simplify=None, texture=None):
         """The surface {one-step opacity = level} of the field as a triangle mesh, extracted on the device (ops.mesh_from_lattice):
         a Mesh of vertices [nv, 3] fp32 in the scene box's coordinates, triangles [nt, 3] int32 with normals pointing out of the
         opaque side, and the box (lo, hi), the size (shape) and the level of the lattice the surface was taken on.  What the
@@ -416,7 +443,12 @@ class BAT_VMSplit(torch.nn.Module):
         point_colors on the SIMPLIFIED vertices against their new normals -- what the field says at the representative, not an
         average, and fewer points to shade.  Mesh.normals are then the clusters' (the normalised sum of their members'),
         n_degenerate_normals the zero ones among them, and Mesh.simplified = (cells, n_vertices_in, n_triangles_in,
-        n_dropped_invalid, n_collapsed).  None launches nothing new."""
+        n_dropped_invalid, n_collapsed).  None launches nothing new.
+        texture: S, an integer from 4 to 64 -- Mesh.texture = bake_texture(vertices, triangles, normals, block=S), baked last, on
+        the mesh as it is returned (after keep_largest / min_points and after simplify); the normals are then computed whether
+        asked for or not.  An empty mesh gets none.  None launches nothing new and leaves every other field as it was."""
+        if texture is not None:
+            ops.texture_layout(1, texture)                     # (a ValueError for what is no block size, before any work)
         if simplify is not None:
             if isinstance(simplify, bool) or not isinstance(simplify, (int, float)) or not (math.isfinite(simplify) and simplify >= 1):
                 raise ValueError("extract_mesh: simplify is None or a finite number >= 1, in lattice spacings (got %r)" % (simplify,))
@@ -430,7 +462,7 @@ class BAT_VMSplit(torch.nn.Module):
             vol, lo, hi = ops.cap_lattice(vol, lo, hi)
         vertices, triangles = ops.mesh_from_lattice(vol, level, lo, hi)
         nrm = col = n_bad = simplified = None
-        if normals or colors or simplify is not None:
+        if normals or colors or simplify is not None or texture is not None:
             nrm, n_bad = self.point_normals(vertices)
         if simplify is not None:
             cells = [int(math.ceil((n - 1) / float(simplify))) for n in vol.shape]
@@ -443,8 +475,12 @@ class BAT_VMSplit(torch.nn.Module):
             zero = (nrm == 0).all(-1, keepdim=True)
             col = self.point_colors(vertices, torch.where(zero, nrm.new_tensor([0.0, 0.0, -1.0]), -nrm), view_pe_progress,
                                     fea_pe_progress)
+        tex = None
+        if texture is not None and triangles.shape[0] > 0:
+            tex = self.bake_texture(vertices, triangles, nrm, block=texture, view_pe_progress=view_pe_progress,
+                                    fea_pe_progress=fea_pe_progress)
         return Mesh(vertices, triangles, tuple(lo), tuple(hi), tuple(vol.shape), float(level), nrm if normals else None, col,
-                    n_components, n_bad if normals else None, simplified)
+                    n_components, n_bad if normals else None, simplified, tex)
 
     @torch.no_grad()
     def updateAlphaMask(self, gridSize=(200, 200, 200)):
