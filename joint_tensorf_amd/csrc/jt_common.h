@@ -167,7 +167,10 @@ __device__ inline bool mask_keep(const Dev& D, const float p[3]) {
     const float ix = ((g + 1.f) * 0.5f) * (float)(D.md[a] - 1);
     const float fl = floorf(ix);
     i0[a] = (int)fl;
-    f[a] = ix - fl;
+    // the fraction of the ROUNDED ix, as grid_sample takes it (exact).  Left to the compiler, the product is contracted into
+    // the subtraction: where ix rounds onto a node from above, that fraction is a tiny positive number instead of 0, the
+    // upper corner counts, and a sample the reference drops is kept (tests/test_gpu_mask_edges.py, the one-ulp family)
+    f[a] = add_rn(ix, -fl);
   }
   bool keep = false;
 #pragma unroll

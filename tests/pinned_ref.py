@@ -366,16 +366,25 @@ def _pinned_line(line, g, use_taps=False):
     return pinned_taps(line, torch.zeros_like(g), g)
 
 
+def _pinned_mask_sample(alpha_mask, xyz):
+    """alpha_mask_sample whose `> 0` is tests/mask_ref.py's keep on the fp32 sample positions the pinned sampler produced
+    (xyz holds fp32 values): 1 where the mask keeps the sample, 0 where it drops it"""
+    from tests import mask_ref
+    return mask_ref.keep(alpha_mask[0], alpha_mask[1], xyz).to(xyz.device).to(xyz.dtype)
+
+
 def reference(cfg, params, o, d, S, cot, ndc=False, white=True, app_mask=None, relu=None, keep=False, decide_dev=None,
-              ray_only=False):
+              ray_only=False, alpha_mask=None):
     """The oracle in params' dtype on params' device for rays (o, d) with the discrete decisions pinned; returns outputs,
     gradients of every parameter (T), the ray gradients and per factor M and F (see the module docstring).  keep=True
     also returns the recorded samples: (factor name, factor, samples [C, P], U [C, P]) per sampling call.  ray_only: the
-    outputs and the ray gradients alone (the parameters should then not require a gradient; T, M and F are empty)."""
+    outputs and the ray gradients alone (the parameters should then not require a gradient; T, M and F are empty).
+    alpha_mask: (volume [Z, Y, X], aabb [2, 3]) of an alpha mask, handed on to O.render with its decision pinned as the
+    geometry is (_pinned_mask_sample)."""
     dev, dt = params["density_plane"][0].device, params["density_plane"][0].dtype
     names = {} if ray_only else {id(v): n for n, v in O.flat_params(params)}
     rec = []
-    saved = (O._sample_plane, O._sample_line, O.sample_ray, O.sample_ray_ndc, O.normalize_coord)
+    saved = (O._sample_plane, O._sample_line, O.sample_ray, O.sample_ray_ndc, O.normalize_coord, O.alpha_mask_sample)
 
     def wrap(fn):
         def f(factor, *a):
@@ -389,12 +398,13 @@ def reference(cfg, params, o, d, S, cot, ndc=False, white=True, app_mask=None, r
     O._sample_plane, O._sample_line = wrap(_pinned_plane), wrap(_pinned_line)
     O.sample_ray, O.sample_ray_ndc = _pinned_samplers(decide_dev)
     O.normalize_coord = _pinned_normalize
+    O.alpha_mask_sample = _pinned_mask_sample
     rep = {}
     try:
         rgb, depth, acc = O.render(cfg, params, oc, dc, S, white_bg=white, ndc_ray=ndc, app_mask_override=app_mask,
-                                   relu_masks_override=relu, relu_report=rep)
+                                   relu_masks_override=relu, relu_report=rep, alpha_mask=alpha_mask)
     finally:
-        O._sample_plane, O._sample_line, O.sample_ray, O.sample_ray_ndc, O.normalize_coord = saved
+        O._sample_plane, O._sample_line, O.sample_ray, O.sample_ray_ndc, O.normalize_coord, O.alpha_mask_sample = saved
     tot = (rgb * cot[0].to(dev).to(dt)).sum() + (acc * cot[1].to(dev).to(dt)).sum()
     if tot.requires_grad:
         tot.backward(retain_graph=not ray_only)
@@ -432,7 +442,9 @@ def run_reference(tf, kind, hip, o, d, S, cot_seed=0, ndc=False, white=True, ste
     """the fp64 reference of run_hip's iteration, pinned to its shading mask and ReLU signs.  It runs on the CPU (the
     same fp64 arithmetic; the GPU's fp64 atomics in grid_sample's backward made the long-line rows ten times slower),
     with the fp32 sample decisions taken on the GPU like the product path's.  ray_only (a pose-only iteration): outputs
-    and ray gradients alone, the rays taken in slices of about slice_entries shaded samples (rays are independent)."""
+    and ray gradients alone, the rays taken in slices of about slice_entries shaded samples (rays are independent).
+    When tf carries an alpha mask (tf.alphaMask), the reference renders with it, its decision pinned (reference)."""
+    am = None if tf.alphaMask is None else (tf.alphaMask.alpha_volume[0, 0].detach().cpu(), tf.alphaMask.aabb.detach().cpu())
     cfg = scene_cfg(tf.aabb.view(-1).tolist(), tf.gridSize.tolist(), [float(tf.near_far[0]), float(tf.near_far[1])], kind,
                     step_ratio, thres, "cpu", torch.float64)
     relu = None if hip["relu"] is None else [m.cpu() for m in hip["relu"]]
@@ -453,7 +465,8 @@ def run_reference(tf, kind, hip, o, d, S, cot_seed=0, ndc=False, white=True, ste
             e1 = int(ends[b - 1])
             r = None if relu is None else [m[e0:e1] for m in relu]
             part = reference(cfg, params, o[a:b].cpu(), d[a:b].cpu(), S, (cot[0][a:b], cot[1][a:b]), ndc=ndc, white=white,
-                             app_mask=mask[a:b], relu=r, decide_dev=tf.density_plane[0].device, ray_only=True)
+                             app_mask=mask[a:b], relu=r, decide_dev=tf.density_plane[0].device, ray_only=True,
+                             alpha_mask=am)
             for k, v in part.pop("relu").items():
                 rep[k] = max(rep.get(k, 0.0), v) if k == "max_abs" else rep.get(k, 0) + v
             parts.append(part)
@@ -462,7 +475,7 @@ def run_reference(tf, kind, hip, o, d, S, cot_seed=0, ndc=False, white=True, ste
         out["relu"] = rep
         return out
     return reference(cfg, params, o.cpu(), d.cpu(), S, cotangents(o.shape[0], cot_seed), ndc=ndc, white=white,
-                     app_mask=hip["shade_mask"].cpu(), relu=relu, decide_dev=tf.density_plane[0].device)
+                     app_mask=hip["shade_mask"].cpu(), relu=relu, decide_dev=tf.density_plane[0].device, alpha_mask=am)
 
 
 def far_node_samples(aabb, grid, near_far, o, d, S, ndc=False, step_ratio=0.5, device="cpu"):

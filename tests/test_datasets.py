@@ -227,7 +227,10 @@ def test_data_load_precedence(tmp_path, monkeypatch, capsys):
     opt = _small_opt(data=dict(image_size=[12, 12], num_views=3, synthetic=False, root=str(tmp_path / "sets"), scene="shapes"))
     ds = jdata.load(opt, "val")
     assert type(ds).__module__ == "data.blender" and ds.split == "val" and opt.data.dataset_class == "data.blender.Dataset"
-    _forget_data_modules(monkeypatch)
+    # (popped, not monkeypatch.delitem: its undo would put the stand-in module back for every later test of the process,
+    #  and tests/test_gpu_ingest.py's in-process training run would load it in place of the native loader)
+    for k in [k for k in sys.modules if k == "data" or k.startswith("data.")]:
+        del sys.modules[k]
 
 
 def test_native_loader_needs_a_known_dataset(tmp_path, monkeypatch):

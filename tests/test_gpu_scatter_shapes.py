@@ -119,12 +119,15 @@ def _ndc_setup(grid, rays, seed, n_far_side=0):
 
 
 def _check_row(tag, kind, grid, aabb, o, d, S, cd=16, variant="mfma", det=False, ndc=False, expect=(), near_far=(0.5, 40.0),
-               long_line=True):
+               long_line=True, tf=None):
+    """tf: a prepared scene of `kind` on `grid` (tests/test_gpu_mask_edges.py hands one with an alpha mask set) instead of
+    the one P.build_scene makes"""
     import time
     from joint_tensorf_amd._lib import lib
     from tests.test_gpu_parity import kernel_variant
     t0 = time.time()
-    tf = P.build_scene(kind, grid, aabb, DEV, cd=cd, near_far=near_far)
+    if tf is None:
+        tf = P.build_scene(kind, grid, aabb, DEV, cd=cd, near_far=near_far)
     prev = lib.jt_set_deterministic(1 if det else 0)
     try:
         with kernel_variant(variant):

@@ -393,7 +393,22 @@ def test_alpha_mask_update_and_shrink_vs_golden():
     tf.alphaMask = type(tf.alphaMask)(DEV, fx.t("mask.aabb", DEV), fx.t("mask.alpha_volume", DEV))
     np.testing.assert_allclose(tf.alphaMask.sample_alpha(pts).cpu().numpy(), ref.numpy(), atol=1e-6)
     a_masked = tf.compute_alpha(pts, 0.1).cpu()
-    assert float(a_masked[ref <= 0].abs().max()) == 0.0 and float(a_masked[ref > 0].max()) > 0.0
+    assert float(a_masked[ref <= 0].abs().max()) == 0.0
+    # every point the pinned mask decision (tests/mask_ref.py) keeps has the unmasked value: the same kernel, the same bits
+    from tests import mask_ref
+    mask = tf.alphaMask
+    keep = mask_ref.keep(torch.tensor(fx.arrays["mask.alpha_volume"]), torch.tensor(fx.arrays["mask.aabb"]), pts.cpu())
+    tf.alphaMask = None
+    a_plain = tf.compute_alpha(pts, 0.1).cpu()
+    tf.alphaMask = mask
+    assert int(keep.sum()) > 0 and torch.equal(a_masked[keep], a_plain[keep]) and float(a_plain[keep].min()) > 0.0
+    # the masked branch of k_dense_alpha, which the second mask update of a run goes through: the lattice of getDenseAlpha
+    # (every point of it on a node of this mask) against the oracle's masked dense_alpha
+    alpha_m, _ = tf.getDenseAlpha(grid)
+    ref_m, _ = O.dense_alpha(fx.cfg(), fx.params(requires_grad=False), grid,
+                             alpha_mask=(torch.tensor(fx.arrays["mask.alpha_volume"]), torch.tensor(fx.arrays["mask.aabb"])))
+    assert 0 < int((ref_m == 0).sum()) < ref_m.numel()
+    np.testing.assert_allclose(alpha_m.cpu().numpy(), ref_m.numpy(), atol=1e-7, rtol=5e-5)
     # shrink with the reference's box: cropped channel-last factors, snapped box, grid
     fs = Fixture("blender_train_shrunk")
     tf.shrink(fx.t("mask.new_aabb", DEV))
