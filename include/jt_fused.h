@@ -37,6 +37,25 @@ int jt_pose_fused(const JtScene* scene, const JtFactors* factors, const JtMlp* m
                   float* sqerr, float* loss, float* g_rays_o, float* g_rays_d, void* workspace, size_t workspace_bytes,
                   void* stream);
 
+/* jt_pose_fused_workspace_bytes answers 0 for a scene the kernel cannot take: another shading configuration, or a sample
+ * count whose per-workgroup LDS need (MLP weights + eight sin / cos stashes + eight shaded-sample lists of Sp uint16 +
+ * tables) is past 160 KB -- n_samples above 1408 (VM-48 / MLP_Fea) or 4480 (VM-20 / WeakView).  jt_pose_fused returns
+ * JT_ERR_UNSUPPORTED for such a scene without launching.
+ *
+ * Where a launch leaves its per-ray decisions (tests pin their fp64 reference to them).  The workspace is
+ *   [head floats] [slot 0] [slot 1] ...        slot = (workgroup * waves per workgroup + wave), `floats per slot` each;
+ * in every round of a launch, wave w of workgroup b renders ray  round * workgroups * waves + w * workgroups + b  (a launch
+ * of at most 2048 rays is one round: the slot keeps its ray's data after the launch).  A slot is
+ *   six per-sample arrays of Sp = roundup(n_samples, 64) floats: feature, weight, alpha -> d loss / d feature,
+ *     transmittance, in-box flag, RANK (int32: the sample's entry index among the ray's shaded samples, -1 if not shaded)
+ *   Sp / 32 tile blocks of `rows per tile block` x 32 floats (entry e of the ray: block e / 32, column e % 32); rows
+ *     `first sign row` + 2 * layer + h hold the ReLU sign words of hidden layer `layer` (bit mt * 16 + r of the word of
+ *     half h: unit mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h), rows `first rgb row` + c the sample's colour
+ *   Sp / 32 + Sp / 64 rows of 8 partial sums.
+ * out = {head floats, floats per slot, Sp, rows per tile block, first sign row, first rgb row, workgroups a launch of
+ * n_rays rays runs, waves per workgroup}, from the constants the launcher itself uses. */
+int jt_pose_fused_scratch_layout(const JtScene* scene, int n_rays, int64_t out[8]);
+
 
 #ifdef __cplusplus
 }

@@ -166,6 +166,7 @@ SIGNATURES = {
 # the OPTIONAL module include/jt_fused.h declares (libjt_fused.so: the single-launch test-time kernel, loaded on demand)
 FUSED_SIGNATURES = {
     "jt_pose_fused_workspace_bytes": (ctypes.c_size_t, [SP]),
+    "jt_pose_fused_scratch_layout": (I, [SP, I, P]),
     "jt_pose_fused": (I, [SP, FP, MP, P, P, P, I, P, P, I, I, F, P, P, P, P, P, P, P, P, ctypes.c_size_t, P]),
 }
 FUSED_LIB_PATH = os.path.join(HERE, "lib", "libjt_fused.so")

@@ -740,19 +740,52 @@ static long fused_slot_floats(int S) {
   return 6 * Sp + (Sp / 32) * (long)kTileRows * 32 + (Sp / 32 + Sp / 64) * 8;
 }
 
+// Dynamic LDS of k_pose_fused<C> at Sp samples per slot (Sp = S rounded up to 64): the weights, the eight sin / cos stashes, the
+// eight shaded-sample lists and the tables.  The one place the launcher, the workspace probe and the layout query take it from.
+template <class C>
+static size_t fused_lds_bytes(long Sp) {
+  return (size_t)C::LDS_FLOATS * sizeof(float) + (size_t)kFusedWaves * 2 * 16 * 64 * sizeof(float) +
+         (size_t)kFusedWaves * Sp * sizeof(uint16_t) + sizeof(FusedTabs);
+}
+
+static const size_t kFusedLdsLimit = 160 * 1024;
+
+// whether a scene of fused_kind `kind` with S samples per ray fits the kernel's LDS
+static bool fused_lds_fits(int kind, int S) {
+  const long Sp = (S + 63) & ~63;
+  return (kind == 0 ? fused_lds_bytes<CfgBlender>(Sp) : fused_lds_bytes<CfgLlff>(Sp)) <= kFusedLdsLimit;
+}
+
+static int fused_blocks(int n_rays) { return std::min(kFusedBlocks, (n_rays + kFusedWaves - 1) / kFusedWaves); }
+
 extern "C" size_t jt_pose_fused_workspace_bytes(const JtScene* scene) {
-  if (fused_kind(scene) < 0 || scene->n_samples < 1) return 0;
+  const int kind = fused_kind(scene);
+  if (kind < 0 || scene->n_samples < 1 || !fused_lds_fits(kind, scene->n_samples)) return 0;
   return ((size_t)fused_slot_floats(scene->n_samples) * kFusedBlocks * kFusedWaves + kFusedHeadFloats) * sizeof(float);
+}
+
+extern "C" int jt_pose_fused_scratch_layout(const JtScene* scene, int n_rays, int64_t out[8]) {
+  if (!scene || !out || n_rays < 1) return JT_ERR_ARG;
+  const int kind = fused_kind(scene);
+  if (kind < 0 || scene->n_samples < 1 || !fused_lds_fits(kind, scene->n_samples)) return JT_ERR_UNSUPPORTED;
+  out[0] = kFusedHeadFloats;
+  out[1] = fused_slot_floats(scene->n_samples);
+  out[2] = (scene->n_samples + 63) & ~63;
+  out[3] = kTileRows;
+  out[4] = kRowMask;
+  out[5] = kRowRgb;
+  out[6] = fused_blocks(n_rays);
+  out[7] = kFusedWaves;
+  return JT_OK;
 }
 
 template <class C>
 static int launch_fused(const Dev& D, const MlpDev& M, const PeMask& pm, const FusedArgs& A, hipStream_t st) {
-  const size_t lds = (size_t)C::LDS_FLOATS * sizeof(float) + (size_t)kFusedWaves * 2 * 16 * 64 * sizeof(float) +
-                     (size_t)kFusedWaves * A.Sp * sizeof(uint16_t) + sizeof(FusedTabs);
-  if (lds > 160 * 1024) return JT_ERR_UNSUPPORTED;
+  const size_t lds = fused_lds_bytes<C>(A.Sp);
+  if (lds > kFusedLdsLimit) return JT_ERR_UNSUPPORTED;
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_pose_fused<C>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)lds);
-  const int blocks = std::min(kFusedBlocks, (A.R + kFusedWaves - 1) / kFusedWaves);
+  const int blocks = fused_blocks(A.R);
   hipLaunchKernelGGL((k_pose_fused<C>), dim3(blocks), dim3(64 * kFusedWaves), lds, st, D, M, pm, A);
   JT_LAUNCH_CHECK();
   return JT_OK;

@@ -392,9 +392,9 @@ class Graph(torch.nn.Module):
                 and not any(p.requires_grad for p in tf.parameters())):
             return None
         if getattr(tf, "_pose_fused_ok", None) is None:
-            # the single-launch kernel exists for the two BAT shading configurations only (jt_pose_fused_workspace_bytes
-            # returns 0 otherwise): any other scene takes the staged path instead of raising; asked once per
-            # scene object, BEFORE any host draw is consumed
+            # the single-launch kernel exists for the two BAT shading configurations only, up to the sample count its LDS
+            # holds (1 408 / 4 480; jt_pose_fused_workspace_bytes returns 0 otherwise): any other scene takes the staged
+            # path instead of raising; asked once per scene object, BEFORE any host draw is consumed
             from .._lib import fused_lib
             tf._pose_fused_ok = fused_lib().jt_pose_fused_workspace_bytes(
                 tf._render_cfg(self.nerf.n_samples, bool(opt.camera.ndc), bool(opt.nerf.setbg_opaque)).scene()) > 0

@@ -297,6 +297,102 @@ def _run_hip(tf, o, d, S, ndc, white, cot_seed, profile, pose_only):
                 overruns=overruns)
 
 
+def fused_layout(scene, n_rays):
+    """jt_pose_fused_scratch_layout (include/jt_fused.h) as a dict: where a launch of n_rays rays of `scene` (a JtScene)
+    leaves its per-ray decisions.  None when the single-launch kernel does not take the scene."""
+    import ctypes
+    from joint_tensorf_amd._lib import fused_lib
+    out = (ctypes.c_int64 * 8)()
+    if fused_lib().jt_pose_fused_scratch_layout(ctypes.byref(scene), int(n_rays), ctypes.cast(out, ctypes.c_void_p)) != 0:
+        return None
+    keys = ("head", "slot", "Sp", "tile_rows", "row_sign", "row_rgb", "blocks", "waves")
+    return dict(zip(keys, (int(v) for v in out)))
+
+
+def fused_slot_of(lay, n_rays):
+    """the slot index of every ray of a launch [n_rays] (long): in every round wave w of workgroup b renders ray
+    round * blocks * waves + w * blocks + b and owns slot b * waves + w.  Rays of a later round reuse the slots of the
+    first: after the launch a slot holds the data of the LAST ray that used it."""
+    q = torch.arange(n_rays) % (lay["blocks"] * lay["waves"])
+    return (q % lay["blocks"]) * lay["waves"] + q // lay["blocks"]
+
+
+def decode_fused_scratch(ws, lay, n_rays, S, hidden):
+    """The decisions a k_pose_fused launch left in its workspace `ws` (any dtype, viewed as 32-bit words): the shading
+    mask [n_rays, S] (rank >= 0; rank is the sixth of the six per-sample arrays in front of a slot's tile blocks) and the
+    ReLU signs of the two hidden layers, two bool tensors [n, hidden] over the shaded entries in ray-major order,
+    ascending sample (the sign words' bit layout is the record tape's, fullsize_util.read_relu_masks; k_pose_fused's
+    fused_tile_fwd writes relu_signs's word of lane half h to row row_sign + 2 * layer + h, column = entry % 32).  Each
+    ray is read from its own slot (fused_slot_of): for a launch of more than one round the caller must know whose data a
+    slot holds."""
+    words = ws.contiguous().view(torch.int32)      # read where it lies: the workspace of a long-S scene is gigabytes
+    take = lambda idx: words[idx.to(words.device)].cpu()  # noqa: E731
+    Sp, rows = lay["Sp"], lay["tile_rows"]
+    assert S <= Sp and words.numel() >= lay["head"] + lay["blocks"] * lay["waves"] * lay["slot"]
+    base = lay["head"] + fused_slot_of(lay, n_rays) * lay["slot"]                 # [R]
+    rank = take((base[:, None] + 5 * Sp + torch.arange(S)[None]).reshape(-1)).view(n_rays, S)
+    mask = rank >= 0
+    count = mask.sum(1)
+    # a ray's ranks count its shaded samples in ascending order
+    want = torch.cumsum(mask.long(), 1) - 1
+    assert bool((rank[mask] == want[mask]).all()) and bool((rank[~mask] == -1).all()), "rank array is not a prefix count"
+    r_idx = mask.nonzero()[:, 0]
+    e = rank[mask].long()
+    tile0 = base[r_idx] + 6 * Sp + (e // 32) * rows * 32 + e % 32
+    n = int(e.numel())
+    relu = []
+    for layer in range(2):
+        m = torch.zeros(n, hidden, dtype=torch.bool)
+        for h in range(2):
+            word = take(tile0 + (lay["row_sign"] + 2 * layer + h) * 32)
+            for mt in range(hidden // 32):
+                for r in range(16):
+                    m[:, mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h] = ((word >> (mt * 16 + r)) & 1).bool()
+        relu.append(m)
+    return mask, relu, count
+
+
+def run_fused(tf, o, d, S, image, ray_idx, rays_per_view, ndc=False, white=True):
+    """One launch of the single-launch pose kernel (csrc/jt_fused.hip) through the product entry point
+    ops.render_pose_fused, under guard_band, on a freshly zeroed workspace (the `pose_fused` entry of ops._WS is dropped
+    first).  image [views, 3, H, W], ray_idx [rays_per_view] (long).  Returns rgb, depth, opacity, sqerr, loss, g_o, g_d,
+    the shading mask and ReLU signs decoded from the scratch slots (decode_fused_scratch: meaningful as they stand while
+    the launch is one round), the layout, the raw workspace (`ws`, the live tensor) and the guard violations."""
+    from joint_tensorf_amd import ops
+    dev = tf.density_plane[0].device
+    ops._WS.pop((str(dev), "pose_fused"), None)
+    return run_fused_again(tf, o, d, S, image, ray_idx, rays_per_view, ndc=ndc, white=white)
+
+
+def run_fused_again(tf, o, d, S, image, ray_idx, rays_per_view, ndc=False, white=True):
+    """run_fused on the workspace as the previous launch left it"""
+    from joint_tensorf_amd import ops
+    dev = tf.density_plane[0].device
+    R = o.shape[0]
+    og, dg = o.to(dev).requires_grad_(True), d.to(dev).requires_grad_(True)
+    near, far = float(tf.near_far[0]), float(tf.near_far[1])
+    zvals = torch.linspace(near, far, S, device=dev, dtype=torch.float32) if ndc else None
+    cfg = tf._render_cfg(S, ndc, bool(white))
+    guard = guard_band()
+    with guard:
+        out = ops.render_pose_fused(cfg, og, dg, zvals, image.to(dev), ray_idx.to(dev), int(rays_per_view),
+                                    list(tf.density_plane), list(tf.density_line), list(tf.app_plane), list(tf.app_line),
+                                    tf.basis_mat.weight, tf.renderModule.weights())
+        out[0].backward()
+        torch.cuda.synchronize()
+    overruns = guard.violations()
+    bufs = [base for shape, base, n in guard.held if shape == (R * 12 + 1,)]   # the launch's one output allocation
+    assert len(bufs) == 1
+    buf = bufs[0]
+    ws = ops._WS[(str(dev), "pose_fused")]
+    lay = fused_layout(cfg.scene(), R)
+    mask, relu, count = decode_fused_scratch(ws, lay, R, S, tf.featureC)
+    return dict(rgb=out[1].detach().clone(), depth=out[2].detach().clone(), opacity=out[3].detach().clone(),
+                sqerr=buf[5 * R:6 * R].clone(), loss=out[0].detach().clone(), g_o=og.grad.detach().clone(),
+                g_d=dg.grad.detach().clone(), shade_mask=mask, relu=relu if int(mask.sum()) else None, count=count,
+                layout=lay, ws=ws, overruns=overruns, loss_scale=1.0 / (3.0 * R))
+
+
 def _cfg32(cfg):
     c = copy.copy(cfg)
     for k in ("aabb", "aabbSize", "invaabbSize", "units", "stepSize"):
@@ -374,13 +470,16 @@ def _pinned_mask_sample(alpha_mask, xyz):
 
 
 def reference(cfg, params, o, d, S, cot, ndc=False, white=True, app_mask=None, relu=None, keep=False, decide_dev=None,
-              ray_only=False, alpha_mask=None):
+              ray_only=False, alpha_mask=None, loss=None):
     """The oracle in params' dtype on params' device for rays (o, d) with the discrete decisions pinned; returns outputs,
     gradients of every parameter (T), the ray gradients and per factor M and F (see the module docstring).  keep=True
     also returns the recorded samples: (factor name, factor, samples [C, P], U [C, P]) per sampling call.  ray_only: the
     outputs and the ray gradients alone (the parameters should then not require a gradient; T, M and F are empty).
     alpha_mask: (volume [Z, Y, X], aabb [2, 3]) of an alpha mask, handed on to O.render with its decision pinned as the
-    geometry is (_pinned_mask_sample)."""
+    geometry is (_pinned_mask_sample).
+    loss = (target [R, 3], loss_scale): the scalar that is differentiated is loss_scale * ((rgb.clamp(0, 1) - target)^2).sum()
+    instead of the cotangent form (cot is not used; torch's clamp passes the gradient on the closed interval [0, 1]); the
+    result then carries `sqerr` [R] and `loss` as well."""
     dev, dt = params["density_plane"][0].device, params["density_plane"][0].dtype
     names = {} if ray_only else {id(v): n for n, v in O.flat_params(params)}
     rec = []
@@ -405,13 +504,19 @@ def reference(cfg, params, o, d, S, cot, ndc=False, white=True, app_mask=None, r
                                    relu_masks_override=relu, relu_report=rep, alpha_mask=alpha_mask)
     finally:
         O._sample_plane, O._sample_line, O.sample_ray, O.sample_ray_ndc, O.normalize_coord, O.alpha_mask_sample = saved
-    tot = (rgb * cot[0].to(dev).to(dt)).sum() + (acc * cot[1].to(dev).to(dt)).sum()
+    extra = {}
+    if loss is not None:
+        sq = ((rgb.clamp(0, 1) - loss[0].to(dev).to(dt)) ** 2).sum(-1)
+        tot = float(loss[1]) * sq.sum()
+        extra = dict(sqerr=sq.detach(), loss=tot.detach())
+    else:
+        tot = (rgb * cot[0].to(dev).to(dt)).sum() + (acc * cot[1].to(dev).to(dt)).sum()
     if tot.requires_grad:
         tot.backward(retain_graph=not ray_only)
     if ray_only:
         return dict(samples=[], rgb=rgb.detach(), depth=depth.detach(), opacity=acc.detach(), T={}, M={}, F={},
                     g_o=torch.zeros_like(oc) if oc.grad is None else oc.grad.detach(),
-                    g_d=torch.zeros_like(dc) if dc.grad is None else dc.grad.detach(), relu=rep)
+                    g_d=torch.zeros_like(dc) if dc.grad is None else dc.grad.detach(), relu=rep, **extra)
     T = {n: (torch.zeros_like(v) if v.grad is None else v.grad.detach().clone()) for n, v in O.flat_params(params)}
     M = {n: torch.zeros_like(T[n]) for n in FACTORS}
     F = {n: torch.zeros_like(T[n]) for n in FACTORS}
@@ -426,7 +531,7 @@ def reference(cfg, params, o, d, S, cot, ndc=False, white=True, app_mask=None, r
     return dict(samples=kept, rgb=rgb.detach(), depth=depth.detach(), opacity=acc.detach(), T=T, M=M,
                 F={n: v > 0 for n, v in F.items()},
                 g_o=torch.zeros_like(oc) if oc.grad is None else oc.grad.detach(),
-                g_d=torch.zeros_like(dc) if dc.grad is None else dc.grad.detach(), relu=rep)
+                g_d=torch.zeros_like(dc) if dc.grad is None else dc.grad.detach(), relu=rep, **extra)
 
 
 def params_of(tf, dtype=torch.float64):
@@ -438,12 +543,13 @@ def params_of(tf, dtype=torch.float64):
 
 
 def run_reference(tf, kind, hip, o, d, S, cot_seed=0, ndc=False, white=True, step_ratio=0.5, thres=1e-7, ray_only=False,
-                  slice_entries=1 << 16):
+                  slice_entries=1 << 16, loss=None):
     """the fp64 reference of run_hip's iteration, pinned to its shading mask and ReLU signs.  It runs on the CPU (the
     same fp64 arithmetic; the GPU's fp64 atomics in grid_sample's backward made the long-line rows ten times slower),
     with the fp32 sample decisions taken on the GPU like the product path's.  ray_only (a pose-only iteration): outputs
     and ray gradients alone, the rays taken in slices of about slice_entries shaded samples (rays are independent).
-    When tf carries an alpha mask (tf.alphaMask), the reference renders with it, its decision pinned (reference)."""
+    When tf carries an alpha mask (tf.alphaMask), the reference renders with it, its decision pinned (reference).
+    loss = (target [R, 3], loss_scale): the loss form of `reference` (the result carries sqerr [R] and loss)."""
     am = None if tf.alphaMask is None else (tf.alphaMask.alpha_volume[0, 0].detach().cpu(), tf.alphaMask.aabb.detach().cpu())
     cfg = scene_cfg(tf.aabb.view(-1).tolist(), tf.gridSize.tolist(), [float(tf.near_far[0]), float(tf.near_far[1])], kind,
                     step_ratio, thres, "cpu", torch.float64)
@@ -466,16 +572,20 @@ def run_reference(tf, kind, hip, o, d, S, cot_seed=0, ndc=False, white=True, ste
             r = None if relu is None else [m[e0:e1] for m in relu]
             part = reference(cfg, params, o[a:b].cpu(), d[a:b].cpu(), S, (cot[0][a:b], cot[1][a:b]), ndc=ndc, white=white,
                              app_mask=mask[a:b], relu=r, decide_dev=tf.density_plane[0].device, ray_only=True,
-                             alpha_mask=am)
+                             alpha_mask=am, loss=None if loss is None else (loss[0][a:b], loss[1]))
             for k, v in part.pop("relu").items():
                 rep[k] = max(rep.get(k, 0.0), v) if k == "max_abs" else rep.get(k, 0) + v
             parts.append(part)
             a = b
         out = {k: torch.cat([p[k] for p in parts]) for k in ("rgb", "depth", "opacity", "g_o", "g_d")}
+        if loss is not None:
+            out["sqerr"] = torch.cat([p["sqerr"] for p in parts])
+            out["loss"] = sum(p["loss"] for p in parts)
         out["relu"] = rep
         return out
     return reference(cfg, params, o.cpu(), d.cpu(), S, cotangents(o.shape[0], cot_seed), ndc=ndc, white=white,
-                     app_mask=hip["shade_mask"].cpu(), relu=relu, decide_dev=tf.density_plane[0].device, alpha_mask=am)
+                     app_mask=hip["shade_mask"].cpu(), relu=relu, decide_dev=tf.density_plane[0].device, alpha_mask=am,
+                     loss=loss)
 
 
 def far_node_samples(aabb, grid, near_far, o, d, S, ndc=False, step_ratio=0.5, device="cpu"):

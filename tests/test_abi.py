@@ -63,7 +63,8 @@ def test_optional_fused_module():
     single-launch kernel (slower than what it would replace -- out of libjt_render.so)."""
     funcs = _header_functions("jt_fused.h")
     from joint_tensorf_amd import _lib
-    assert set(funcs) == set(_lib.FUSED_SIGNATURES) == {"jt_pose_fused", "jt_pose_fused_workspace_bytes"}
+    assert set(funcs) == set(_lib.FUSED_SIGNATURES) == {"jt_pose_fused", "jt_pose_fused_workspace_bytes",
+                                                             "jt_pose_fused_scratch_layout"}
     for name, nargs in funcs.items():
         assert len(_lib.FUSED_SIGNATURES[name][1]) == nargs, (name, nargs)
     so = ctypes.CDLL(_lib.FUSED_LIB_PATH)

@@ -231,3 +231,46 @@ def test_flat_gradient_buffer_zeroes_only_what_nobody_overwrites():
             v.fill_(1.0)
     assert float(flat[24:32].abs().sum()) == 0.0 and float(flat[40:52].abs().sum()) == 0.0
     assert float(sum(v.sum() for vs in (views[0], views[2]) for v in vs)) == 5 * 4 + 3 + 2 * 3
+
+
+def _fused_scene(kind, S):
+    from joint_tensorf_amd import _lib
+    s = _lib.JtScene()
+    ca, app, hid, mlp = (48, 27, 64, _lib.JT_MLP_FEA) if kind == "blender" else (20, 20, 32, _lib.JT_MLP_WEAKVIEW)
+    s.n_comp_density, s.n_comp_app, s.app_dim, s.mlp_hidden, s.mlp_kind = 16, ca, app, hid, mlp
+    s.view_pe = s.fea_pe = 2
+    s.n_samples = S
+    return s
+
+
+# the largest sample count the single-launch pose kernel takes, per scene kind (tests/test_gpu_pose_fused_edges.py derives it)
+FUSED_S_MAX = {"blender": 1408, "llff": 4480}
+
+
+@pytest.mark.parametrize("kind", ["blender", "llff"])
+def test_fused_probe_knows_the_lds_limit(kind):
+    """jt_pose_fused_workspace_bytes is what model/bat_hip.py's render_test_fused asks before it takes the single-launch
+    kernel: it must answer 0 for a sample count whose shaded-sample lists do not fit the kernel's LDS (launch_fused
+    returns JT_ERR_UNSUPPORTED there), so that such a scene takes the staged path instead of raising in the middle of
+    test-time optimisation.  Both sides of the limit, and the layout query with it."""
+    import ctypes
+    from joint_tensorf_amd._lib import fused_lib
+    from tests import pinned_ref as P
+    lib = fused_lib()
+    s_max = FUSED_S_MAX[kind]
+    for S in (1, 64, 65, s_max - 64, s_max - 63, s_max):
+        sc = _fused_scene(kind, S)
+        lay = P.fused_layout(sc, 9)
+        Sp = (S + 63) // 64 * 64
+        assert lay is not None and lay["Sp"] == Sp and lay["blocks"] == 2 and lay["waves"] == 8, (S, lay)
+        assert lib.jt_pose_fused_workspace_bytes(ctypes.byref(sc)) == 4 * (lay["head"] + 2048 * lay["slot"]), S
+    for S in (s_max + 1, s_max + 64, s_max + 65, 65535):
+        sc = _fused_scene(kind, S)
+        assert lib.jt_pose_fused_workspace_bytes(ctypes.byref(sc)) == 0, S
+        assert P.fused_layout(sc, 9) is None, S
+    # workgroups per launch: eight rays each, 256 at the most
+    sc = _fused_scene(kind, 16)
+    assert [P.fused_layout(sc, n)["blocks"] for n in (1, 8, 9, 17, 2040, 2041, 2048, 2057, 100000)] == \
+        [1, 1, 2, 3, 255, 256, 256, 256, 256]
+    sc.view_pe = 4   # another shading configuration: not this kernel's
+    assert lib.jt_pose_fused_workspace_bytes(ctypes.byref(sc)) == 0 and P.fused_layout(sc, 9) is None

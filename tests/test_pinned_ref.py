@@ -14,9 +14,7 @@ KAPPA = max(KAPPA_GPU.values())   # the largest kappa tests/test_gpu_scatter_sha
 FUZZ_TOL = 3e-3         # test_gpu_fuzz.py: max |G - T| <= 3e-3 max |T|
 
 
-def _scene(seed=0, grid=(6, 5, 11), rays=(6, 12, 4)):
-    grid = list(grid)
-    aabb = P.thin_box(grid)
+def _scene_params(seed, grid):
     cd, ca, app_dim, hid = 4, 6, 5, 16
     g = torch.Generator().manual_seed(seed)
     dt = torch.float64
@@ -37,7 +35,14 @@ def _scene(seed=0, grid=(6, 5, 11), rays=(6, 12, 4)):
                     w3=0.3 * torch.randn(3, hid, generator=g, dtype=dt), b3=0.1 * torch.randn(3, generator=g, dtype=dt))
     for _, v in O.flat_params(p):
         v.requires_grad_(True)
-    cfg = P.scene_cfg(aabb, grid, [0.5, 40.0], "blender", 0.5, 1e-7, "cpu", dt)
+    return p
+
+
+def _scene(seed=0, grid=(6, 5, 11), rays=(6, 12, 4)):
+    grid = list(grid)
+    aabb = P.thin_box(grid)
+    p = _scene_params(seed, grid)
+    cfg = P.scene_cfg(aabb, grid, [0.5, 40.0], "blender", 0.5, 1e-7, "cpu", torch.float64)
     o, d = P.ray_set(aabb, *rays, seed=seed)
     S = 2 * grid[2] + 6
     ref = P.reference(cfg, p, o, d, S, P.cotangents(o.shape[0], seed), keep=True)
@@ -214,3 +219,73 @@ def test_census_counts_tiles_per_chunk():
     assert c == dict(shaded=160, tiles=[2, 2, 1], far_tiles=3, plain_tiles=2, far_entries=3), c
     c = P.census(far[..., None].expand(3, 100, 3), torch.zeros_like(mask))
     assert c == dict(shaded=0, tiles=[], far_tiles=0, plain_tiles=0, far_entries=0), c
+
+
+# ---- the additions for the single-launch pose kernel (tests/test_gpu_pose_fused_edges.py) -------------------------------------
+def test_loss_form_equals_cotangent_form():
+    """d / d rays of loss_scale * sum (clamp(rgb) - target)^2 is the cotangent form with cot = 2 loss_scale (rgb - target)
+    taken from the reference's own rgb (no ray that meets the scene has a colour on the clamp's ends), and nothing on the opacity"""
+    grid = [6, 5, 11]
+    aabb = P.thin_box(grid)
+    o, d = P.ray_set(aabb, 6, 12, 4, seed=0)
+    S = 2 * grid[2] + 6
+    R = o.shape[0]
+    p = _scene_params(0, grid)
+    for _, v in O.flat_params(p):
+        v.requires_grad_(False)
+    cfg = P.scene_cfg(aabb, grid, [0.5, 40.0], "blender", 0.5, 1e-7, "cpu", torch.float64)
+    target = torch.rand(R, 3, generator=torch.Generator().manual_seed(4), dtype=torch.float64)
+    scale = 1.0 / (3 * R)
+    a = P.reference(cfg, p, o, d, S, None, ray_only=True, loss=(target, scale))
+    hit = a["opacity"] > 0      # (a ray that misses is the background, exactly 1, and has no gradient in either form)
+    assert int(hit.sum()) >= 12 and float(a["rgb"][hit].min()) > 0.0 and float(a["rgb"][hit].max()) < 1.0
+    cot = (2 * scale * (a["rgb"] - target), torch.zeros(R, dtype=torch.float64))
+    b = P.reference(cfg, p, o, d, S, cot, ray_only=True)
+    assert torch.equal(a["rgb"], b["rgb"]) and torch.equal(a["opacity"], b["opacity"])
+    assert float(a["g_o"].abs().max()) > 0 and float(a["g_d"].abs().max()) > 0
+    for k in ("g_o", "g_d"):
+        assert float((a[k] - b[k]).abs().max()) <= 1e-13 * float(b[k].abs().max()), k
+    assert torch.allclose(a["sqerr"], ((a["rgb"] - target) ** 2).sum(-1), rtol=0, atol=1e-15)
+    assert abs(float(a["loss"]) - scale * float(a["sqerr"].sum())) <= 1e-15
+
+
+def test_fused_scratch_decoder_returns_what_was_put_in():
+    """a workspace filled by hand from the layout query's numbers: 9 rays of a blender scene at S = 70 (Sp = 128: two
+    workgroups, ray 8 alone in the second), among them a ray with 0 shaded samples and one with 33 (a second tile block)"""
+    from tests.test_host_logic import _fused_scene
+    S, R, hid = 70, 9, 64
+    lay = P.fused_layout(_fused_scene("blender", S), R)
+    assert lay["Sp"] == 128 and lay["blocks"] == 2
+    g = torch.Generator().manual_seed(0)
+    counts = [0, 33, 1, 32, 31, 5, 0, 64, 3]
+    ws = torch.randint(-2 ** 31, 2 ** 31 - 1, (lay["head"] + 16 * lay["slot"],), generator=g, dtype=torch.int64).to(torch.int32)
+    mask = torch.zeros(R, S, dtype=torch.bool)
+    signs = [[], []]
+    for r, n in enumerate(counts):
+        b, w = r % lay["blocks"], r // lay["blocks"]          # ray = w * blocks + b in a launch of one round
+        base = lay["head"] + (b * lay["waves"] + w) * lay["slot"]
+        pick = torch.randperm(S, generator=g)[:n].sort().values
+        mask[r, pick] = True
+        rank = torch.full((lay["Sp"],), -1, dtype=torch.int32)
+        rank[pick] = torch.arange(n, dtype=torch.int32)
+        ws[base + 5 * lay["Sp"]:base + 6 * lay["Sp"]] = rank
+        for layer in range(2):
+            m = torch.rand(n, hid, generator=g) < 0.5
+            signs[layer].append(m)
+            for e in range(n):
+                for h in range(2):
+                    word = 0
+                    for mt in range(hid // 32):
+                        for rr in range(16):
+                            if bool(m[e, mt * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * h]):
+                                word |= 1 << (mt * 16 + rr)
+                    word = word - (1 << 32) if word >= 1 << 31 else word
+                    ws[base + 6 * lay["Sp"] + (e // 32) * lay["tile_rows"] * 32 + (lay["row_sign"] + 2 * layer + h) * 32 + e % 32] = word
+    got_mask, got_relu, count = P.decode_fused_scratch(ws, lay, R, S, hid)
+    assert torch.equal(got_mask, mask) and count.tolist() == counts
+    for layer in range(2):
+        assert torch.equal(got_relu[layer], torch.cat(signs[layer])), layer
+    # the slots of a second round are those of the first
+    lay2 = dict(lay, blocks=256)
+    assert torch.equal(P.fused_slot_of(lay2, 2057)[2048:], P.fused_slot_of(lay2, 2057)[:9])
+    assert P.fused_slot_of(lay2, 2057)[:9].tolist() == [8 * b for b in range(9)] and int(P.fused_slot_of(lay2, 2057)[256]) == 1
