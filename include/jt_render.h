@@ -42,9 +42,11 @@ extern "C" {
  * jt_image_ingest / jt_image_ingest_workspace_bytes; 1207: + jt_shade_backward_plan / jt_march_backward_plan; 1208: + jt_mesh_count / jt_mesh_emit;
  * 1209: + jt_components_init / jt_components_sweep / jt_component_sizes, jt_density_gradient, JT_COMPONENTS_TILE; 1210: +
  * jt_raster_project / jt_raster_draw / jt_raster_resolve, JT_RASTER_*; 1211: + jt_mesh_unwarp_ndc / jt_mesh_filter_count / jt_mesh_filter_emit,
- * JT_UNWARP_*; 1212: + jt_simplify_keys / jt_simplify_clusters / jt_simplify_triangles, JT_SIMPLIFY_*.  Additions bump the last two
- * digits, anything a caller built against the old header would get wrong bumps the hundreds). */
-#define JT_VERSION 1213
+ * JT_UNWARP_*; 1212: + jt_simplify_keys / jt_simplify_clusters / jt_simplify_triangles, JT_SIMPLIFY_*; 1213: + jt_texture_texels /
+ * jt_texture_pack / jt_raster_resolve_texture, JT_TEXTURE_*; 1214: + jt_visible_tally / jt_visible_fold / jt_visible_mark /
+ * jt_visible_spread / jt_mesh_select_count.  Additions bump the last two digits, anything a caller built against the old header
+ * would get wrong bumps the hundreds). */
+#define JT_VERSION 1214
 
 #define JT_OK 0
 #define JT_ERR_ARG 1         /* null pointer / bad size */
@@ -827,6 +829,39 @@ int jt_texture_pack(const float* rgb, const uint8_t* valid, int S, int cols, lon
 int jt_raster_resolve_texture(const uint64_t* zbuf, const float* screen, int n_vertices, const int32_t* triangles,
                               long n_triangles, int n_views, int H, int W, const uint8_t* atlas, int S, int cols, int H_atlas,
                               int W_atlas, const float* background, int32_t* tri, float* depth, float* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Visible surface (csrc/jt_visible.hip): which triangles of a mesh its cameras see, decided from what jt_raster_draw leaves --
+ * the index of the nearest triangle in the low word of every pixel's 64-bit key, decided in integers, the same bits on every run.
+ * Integer work throughout; the only atomics are integer additions, so no result depends on the order of execution and a NumPy
+ * statement of this comment reproduces the kernels bit for bit (tests/visible_ref.py).  No resolve is needed.
+ *
+ *   jt_visible_tally: zbuf [n_views][H][W] uint64 as jt_raster_draw leaves it -> pix [n_views][n_triangles] uint32, zeroed by the
+ *     caller: for every pixel whose key is not all-ones, pix[view][key & 0xffffffff] += 1.  A low word >= n_triangles is skipped,
+ *     never used as an index.  Lanes take consecutive pixels and a wave adds a run of equal (view, index) once, with the run's
+ *     length, from its first lane; a run ends at a view boundary (H W need not be a multiple of 64).  With JT_VISIBLE_RUNS=0 in
+ *     the environment (read at every call) one atomic per counted pixel instead: the same sums.
+ *   jt_visible_fold: one lane per triangle, no atomics: views[t] += #{v : pix[v][t] >= min_pixels} (int32) and pixels[t] += sum_v
+ *     pix[v][t] (int64), both read and written: slabs of views compose by one call per slab.  min_pixels >= 1.
+ *   jt_visible_mark: flag[v] = 1 for the three vertices of every triangle with visible[t] != 0 whose ids all lie in [0, n_vertices)
+ *     (flag [n_vertices] uint8, zeroed by the caller; several lanes may store the same 1; no atomics);
+ *   jt_visible_spread: visible_out[t] = visible_in[t] | (ids in range and a flag set on one of them).  The step between the two is
+ *     a grid-wide dependency, hence two launches; `rings` applications of the pair grow the set by `rings` rings of vertex
+ *     neighbours.  visible_out may not alias visible_in.
+ *   jt_mesh_select_count: the per-triangle counterpart of jt_mesh_filter_count: keep_out[t] = 1 iff keep_in[t] != 0 and the three
+ *     ids lie in [0, n_vertices), used[v] = 1 for every vertex of a kept triangle (used [n_vertices], zeroed by the caller; no
+ *     atomics).  The caller scans keep_out and used and compacts with jt_mesh_filter_emit, as after jt_mesh_filter_count.
+ * One launch each on `stream`, nothing else; every argument is checked before the launch.  JT_ERR_ARG for a NULL pointer, a size
+ * or count below 1 or min_pixels < 1; JT_ERR_UNSUPPORTED when n_views H W, n_vertices or 3 n_triangles reaches 2^31. */
+int jt_visible_tally(const uint64_t* zbuf, int n_views, int H, int W, long n_triangles, uint32_t* pix, void* stream);
+int jt_visible_fold(const uint32_t* pix, int n_views, long n_triangles, int min_pixels, int32_t* views, int64_t* pixels,
+                    void* stream);
+int jt_visible_mark(const int32_t* triangles, long n_triangles, long n_vertices, const uint8_t* visible, uint8_t* flag,
+                    void* stream);
+int jt_visible_spread(const int32_t* triangles, long n_triangles, long n_vertices, const uint8_t* visible_in, const uint8_t* flag,
+                      uint8_t* visible_out, void* stream);
+int jt_mesh_select_count(const int32_t* triangles, long n_triangles, long n_vertices, const uint8_t* keep_in, uint8_t* keep_out,
+                         uint8_t* used, void* stream);
 
 #ifdef __cplusplus
 }

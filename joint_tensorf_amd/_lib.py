@@ -154,6 +154,11 @@ SIGNATURES = {
     "jt_texture_texels": (I, [P, P, ctypes.c_long, P, ctypes.c_long, I, I, ctypes.c_long, ctypes.c_long, P, P, P, P]),
     "jt_texture_pack": (I, [P, P, I, I, ctypes.c_long, ctypes.c_long, P, I, I, P]),
     "jt_raster_resolve_texture": (I, [P, P, I, P, ctypes.c_long, I, I, I, P, I, I, I, I, P, P, P, P, P]),
+    "jt_visible_tally": (I, [P, I, I, I, ctypes.c_long, P, P]),
+    "jt_visible_fold": (I, [P, I, ctypes.c_long, I, P, P, P]),
+    "jt_visible_mark": (I, [P, ctypes.c_long, ctypes.c_long, P, P, P]),
+    "jt_visible_spread": (I, [P, ctypes.c_long, ctypes.c_long, P, P, P, P]),
+    "jt_mesh_select_count": (I, [P, ctypes.c_long, ctypes.c_long, P, P, P, P]),
     "jt_blur_batch_forward": (I, [P, I, P]),
     "jt_blur_batch_backward": (I, [P, I, P]),
     "jt_factor_reg_forward": (I, [P, I, I, I, P, P]),
@@ -197,7 +202,7 @@ def fused_lib():
 # the JT_VERSION of include/jt_render.h that SIGNATURES and the struct mirrors above were written against.  A constant, not a
 # read of the header at import time: a vendored copy of the package has no include/ directory beside it (tests/test_abi.py
 # holds this number, the header's and the library's together)
-JT_ABI_VERSION = 1213
+JT_ABI_VERSION = 1214
 
 
 def header_version():

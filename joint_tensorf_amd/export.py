@@ -54,6 +54,21 @@ draw and psnr_vertex_color the same cameras drawn with vertex colours.  Together
 scene it is refused: a chart that is linear in NDC is not linear in world space (perspective-correct charts are not built).
 Without a `--texture.*` option the export writes what it wrote, byte for byte.
 
+`--visible.views=N|all` writes only the surface the training cameras see (ops.visible_triangles; csrc/jt_visible.hip).  The
+level set of a trained field is not one skin: behind the visible surface the field is unsupervised, and hollow interiors,
+enclosed pockets and shells are extracted like everything else -- connected to the outer surface or larger than it, so
+`--surface.keep_largest` keeps them.  The mesh is drawn from N training cameras (evenly spaced over the set, as
+`--preview.views` picks them) at `--visible.size=[H,W]` (default data.image_size) by the device rasteriser; a triangle stays
+when it is the nearest one at `--visible.min_pixels` (1) pixel centres or more in `--visible.min_views` (1) views or more, or
+lies within `--visible.grow` (1) rings of vertex neighbours of such a triangle; `--visible.cull=true` drops back faces while
+deciding.  The stage runs after `--simplify.cell` and before colours and `--texture.block`, which are then evaluated only for
+what is written; on a camera.ndc scene the vertices are carried to world space for drawing only and the mask is applied in NDC,
+so it combines with `--texture.block` there and with `--frame.space=world`.  It needs the run's image set.  mesh.ply gains the
+comment `visible views V size H W min_views A min_pixels B grow G cull C from NV NT seen S grown G2 dropped D`, report.json the
+same numbers.  A triangle is seen only if it wins a pixel CENTRE: on an unsimplified fine mesh a triangle is a pixel or two
+across and may win none -- `--visible.grow` and a larger `--visible.size` are the remedies; after `--simplify.cell=4` a
+triangle is tens of pixels across.  Without a `--visible.*` option the export writes what it wrote, byte for byte.
+
 Every other `--key.sub=value` is one of the dotted overrides of joint_tensorf_amd.train."""
 import sys
 
@@ -76,6 +91,10 @@ FRAME_SPACES = ("world", "ndc")
 SIMPLIFY_DEFAULTS = dict(cell=None)
 # the texture atlas baked for the mesh (block: the edge of a block of two charts in texels, an integer from 4 to 64; None = off)
 TEXTURE_DEFAULTS = dict(block=None)
+# the surface the training cameras see (views: how many decide, 0 = off, or "all"; size: [H, W] they are drawn at, None =
+# data.image_size; a triangle is seen when it wins min_pixels pixel centres in min_views views; grow: rings of vertex neighbours
+# kept round the seen ones; cull: back faces are not drawn while deciding)
+VISIBLE_DEFAULTS = dict(views=0, size=None, min_views=1, min_pixels=1, grow=1, cull=False)
 
 
 def _option_group(over, name, defaults):
@@ -102,6 +121,8 @@ def build_options(argv):
                          "[--surface.normals=true|false] [--surface.colors=true|false] [--preview.views=N|all] [--preview.size=[H,W]] "
                          "[--preview.shade=color|normal|depth|texture] [--preview.check=true|false] [--preview.cull=true|false] "
                          "[--frame.space=world|ndc] [--frame.max_depth=D] [--simplify.cell=K] [--texture.block=S] "
+                         "[--visible.views=N|all] [--visible.size=[H,W]] [--visible.min_views=A] [--visible.min_pixels=B] "
+                         "[--visible.grow=G] [--visible.cull=true|false] "
                          "[--data.root=DIR --key.sub=value ...]")
     mesh = _option_group(over, "mesh", MESH_DEFAULTS)
     surface = _option_group(over, "surface", SURFACE_DEFAULTS)
@@ -109,9 +130,14 @@ def build_options(argv):
     frame = _option_group(over, "frame", FRAME_DEFAULTS)
     simplify = _option_group(over, "simplify", SIMPLIFY_DEFAULTS)
     texture = _option_group(over, "texture", TEXTURE_DEFAULTS)
+    visible = _option_group(over, "visible", VISIBLE_DEFAULTS)
     opt = apply_overrides(load_options(name), over)
     opt.mesh, opt.surface, opt.preview, opt.frame, opt.simplify = mesh, surface, preview, frame, simplify
     opt.texture = texture
+    if visible != VISIBLE_DEFAULTS:
+        # (absent: no opt.visible at all, and nothing new is called)
+        _check_visible(visible)
+        opt.visible = visible
     _check_preview(preview)
     _check_simplify(simplify)
     _check_frame(frame, bool(opt.camera.ndc))
@@ -205,6 +231,31 @@ def _check_texture(texture, preview, frame, ndc):
         raise SystemExit("--preview.shade=texture draws the mesh with its texture atlas: name the block size with --texture.block=S")
 
 
+def _check_visible(visible):
+    v = visible.views
+    if v != "all":
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or float(v) != int(v) or int(v) < 0:
+            raise SystemExit("--visible.views is a non-negative integer or all (got %r)" % (v,))
+        visible.views = int(v)
+    size = visible.size
+    if size is not None:
+        size = [size] * 2 if not isinstance(size, list) else size
+        if (len(size) != 2 or any(isinstance(s, bool) or not isinstance(s, (int, float)) or float(s) != int(s)
+                                  or not 1 <= int(s) <= PREVIEW_MAX_SIZE for s in size)):
+            raise SystemExit("--visible.size is one integer or [H, W], each from 1 to %d (got %r)" % (PREVIEW_MAX_SIZE, visible.size))
+        visible.size = [int(s) for s in size]
+    for k, least in (("min_views", 1), ("min_pixels", 1), ("grow", 0)):
+        n = visible[k]
+        if isinstance(n, bool) or not isinstance(n, (int, float)) or float(n) != int(n) or int(n) < least:
+            raise SystemExit("--visible.%s is an integer of at least %d (got %r)" % (k, least, n))
+        visible[k] = int(n)
+    if not isinstance(visible.cull, bool):
+        raise SystemExit("--visible.cull is true or false (got %r)" % (visible.cull,))
+    if visible.views == 0:
+        raise SystemExit("--visible.size / min_views / min_pixels / grow / cull say how visibility is decided: name the deciding "
+                         "views with --visible.views=N or --visible.views=all")
+
+
 def unwarps(opt):
     """whether this export carries the mesh of an NDC scene to world space (opt.frame.space == "world" on camera.ndc)"""
     return bool(opt.camera.ndc) and (opt.get("frame", None) or {}).get("space", None) == "world"
@@ -227,6 +278,10 @@ def main(argv=None):
         # refused before any GPU work: the NDC map is made of the training views' intrinsics
         raise SystemExit("--frame.space=world needs the run's image set (--data.root=DIR, or --data.synthetic=true): sx = fx / cx "
                          "and sy = fy / cy of the NDC map are read from its intrinsics")
+    if (opt.get("visible", None) or {}).get("views", 0) and not has_dataset(opt):
+        # refused before any GPU work: the training cameras decide what is seen
+        raise SystemExit("--visible.views needs the run's image set (--data.root=DIR, or --data.synthetic=true): its cameras "
+                         "decide which triangles are seen")
     if opt.preview.views != 0:
         # refused before any GPU work: the preview draws the mesh from the cameras of cameras.json
         if not has_dataset(opt):

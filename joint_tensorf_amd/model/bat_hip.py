@@ -1095,10 +1095,23 @@ class Model(torch.nn.Module):
         field lives in: <directory>/atlas.png (RGB), mesh.ply with per-face texture coordinates, `comment TextureFile atlas.png`
         and the comment `texture block S atlas W H`, and mesh.obj + mesh.mtl (mesh_io.write_obj).  The result gains `texture` =
         Opt(block, width, height, atlas, obj, mtl), which report.json repeats.  Not together with frame.space = world on a
-        camera.ndc scene (a chart that is linear in NDC is not linear in world space): a ValueError before any work."""
+        camera.ndc scene (a chart that is linear in NDC is not linear in world space): a ValueError before any work.
+
+        opt.visible.views = "all" or N (absent or 0: off, nothing new is called) writes only the surface the training cameras
+        see (extract_mesh(visible=) -> ops.visible_triangles, csrc/jt_visible.hip): N views evenly spaced over the training set
+        as preview.views picks them, drawn at opt.visible.size = [H, W] (default the image set's size; the intrinsics are
+        rescaled); a triangle stays when it is the nearest one at opt.visible.min_pixels (1) pixel centres or more in
+        opt.visible.min_views (1) views or more, or lies within opt.visible.grow (1) rings of vertex neighbours of one that is;
+        opt.visible.cull drops back faces while deciding.  After simplify, before colours and the texture; on a camera.ndc scene
+        the vertices are carried to world space (ndc_frame's map) for drawing only, so it combines with texture.block there and
+        with frame.space = world.  Needs the training set: without one a ValueError before any work.  The PLY gains the comment
+        `visible views V size H W min_views A min_pixels B grow G cull C from NV NT seen S grown G2 dropped D` and the result
+        `visible` = Mesh.visible, which report.json repeats."""
         from .. import eval_io, mesh_io
         mcfg = opt.get("mesh", None) or {}
         unwarp = self.unwarps(opt)
+        if self.visible_views(opt) and self.train_data is None:
+            raise ValueError("export_scene: visible.views needs the training set (its cameras decide what is seen)")
         block = (opt.get("texture", None) or {}).get("block", None)
         if block is not None and unwarp:
             raise ValueError("export_scene: texture.block together with frame.space = world on a camera.ndc scene is not available "
@@ -1127,7 +1140,7 @@ class Model(torch.nn.Module):
                                          cap=bool(mcfg.get("cap", True)), keep_largest=scfg.get("keep_largest", None),
                                          min_points=scfg.get("min_points", None), normals=ext_normals, colors=ext_colors,
                                          simplify=(opt.get("simplify", None) or {}).get("cell", None), **pe,
-                                         **({} if block is None else {"texture": block}))
+                                         **({} if block is None else {"texture": block}), **self.visible_arg(opt))
         if block is not None and mesh.texture is None:
             raise ValueError("export_scene: the mesh is empty (level %r): nothing to texture" % (mesh.level,))
         frame = None
@@ -1145,6 +1158,10 @@ class Model(torch.nn.Module):
             out.simplified = mesh.simplified
             comments.append("simplify cell %g cells %d %d %d from %d %d collapsed %d"
                             % ((float(opt.simplify.cell),) + tuple(mesh.simplified[0]) + tuple(mesh.simplified[1:3]) + (mesh.simplified[4],)))
+        if mesh.visible is not None:
+            out.visible = mesh.visible
+            comments.append("visible views %d size %d %d min_views %d min_pixels %d grow %d cull %d from %d %d seen %d grown %d "
+                            "dropped %d" % tuple(int(v) for v in mesh.visible))
         if frame is not None:
             out.unwarp = frame
             comments.append("unwarp near %r sx %r sy %r" % (frame.near, frame.sx, frame.sy))
@@ -1186,6 +1203,39 @@ class Model(torch.nn.Module):
     def unwarps(opt):
         """whether an export of this run carries its mesh from NDC to world space: opt.frame.space == "world" on camera.ndc"""
         return bool(opt.camera.ndc) and (opt.get("frame", None) or {}).get("space", None) == "world"
+
+    @staticmethod
+    def visible_views(opt):
+        """opt.visible.views: "all", a positive count, or 0 when the visible-surface stage is off"""
+        views = (opt.get("visible", None) or {}).get("views", 0)
+        if views == "all":
+            return views
+        if isinstance(views, bool) or views is None or int(views) != views or int(views) < 0:
+            raise ValueError("visible.views is all or a count (got %r)" % (views,))
+        return int(views)
+
+    @torch.no_grad()
+    def visible_arg(self, opt):
+        """{} or {"visible": ...} for extract_mesh from opt.visible: the deciding training cameras (refined, in the frame of
+        the mesh; evenly spaced over the set as preview_scene picks them) as projection matrices at opt.visible.size, the
+        three thresholds, cull, and ndc_frame's (sx, sy, near) on a camera.ndc scene"""
+        views = self.visible_views(opt)
+        if not views:
+            return {}
+        from .. import mesh_io
+        cfg = opt.visible
+        if self.train_data is None:
+            raise ValueError("visible.views needs the training set (its cameras decide what is seen)")
+        pose, _ = self.get_all_training_poses(opt)
+        n = int(pose.shape[0])
+        k = n if views == "all" else min(views, n)
+        idx = sorted(set(int(round(i * (n - 1) / max(k - 1, 1))) for i in range(k)))
+        H, W = (int(v) for v in (cfg.get("size", None) or (opt.H, opt.W)))
+        intr = self.train_data.all.intr[idx].to(pose.device, torch.float32)
+        proj = mesh_io.projection_matrices(pose[idx].contiguous(), intr, size=(H, W), image_size=(opt.H, opt.W))
+        return {"visible": dict(proj=proj, H=H, W=W, min_views=cfg.get("min_views", 1), min_pixels=cfg.get("min_pixels", 1),
+                                grow=cfg.get("grow", 1), cull=bool(cfg.get("cull", False)),
+                                ndc=self.ndc_frame(opt) if opt.camera.ndc else None)}
 
     def ndc_frame(self, opt):
         """(sx, sy, near) of the NDC map the ray generator applies to this run's training views: sx = fx / cx and sy = fy / cy in
@@ -1273,7 +1323,7 @@ class Model(torch.nn.Module):
             mesh = tf.extract_mesh(res=mcfg.get("res", None), level=float(mcfg.get("level", 0.005)), cap=bool(mcfg.get("cap", True)),
                                    keep_largest=scfg.get("keep_largest", None), min_points=scfg.get("min_points", None),
                                    simplify=(opt.get("simplify", None) or {}).get("cell", None), **extra,
-                                   **({"texture": block} if shade == "texture" else {}))
+                                   **({"texture": block} if shade == "texture" else {}), **self.visible_arg(opt))
             if unwarp:
                 mesh = self.unwarp_mesh(opt, mesh)[0]
         if shade == "texture" and mesh.triangles.shape[0] and mesh.texture is None:
@@ -1404,6 +1454,8 @@ class Model(torch.nn.Module):
                   "n_triangles": int(mesh.triangles.shape[0]), "views": rows, "mean": means}
         if mesh.simplified is not None:
             report["simplified"] = [list(mesh.simplified[0])] + [int(v) for v in mesh.simplified[1:]]
+        if mesh.visible is not None:
+            report["visible"] = [int(v) for v in mesh.visible]
         if mesh.texture is not None:
             lay = mesh.texture.layout
             report["texture"] = {"block": lay.block, "atlas": [lay.width, lay.height], "file": "atlas.png"}

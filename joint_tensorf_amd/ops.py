@@ -2087,6 +2087,198 @@ def rasterize(vertices, triangles, proj, H, W, attrs=None, near=1e-3, cull=False
                status_counts=torch.cat(counts))
 
 
+def visible_tally(zbuf, n_triangles):
+    """jt_visible_tally: pix [V, nt] int32 (holding the uint32 counts) -- how many pixels of every view of zbuf [V, H, W]
+    (raster_draw's) every triangle wins; a fill and one launch"""
+    V, H, W = zbuf.shape
+    pix = torch.zeros(V, n_triangles, device=zbuf.device, dtype=torch.int32)
+    check(lib.jt_visible_tally(ptr(zbuf), V, H, W, n_triangles, ptr(pix), _stream()), "jt_visible_tally")
+    return pix
+
+
+def visible_fold(pix, min_pixels, views, pixels):
+    """jt_visible_fold, one launch: views [nt] int32 += the views of pix [V, nt] with at least min_pixels pixels, pixels [nt]
+    int64 += their sum"""
+    check(lib.jt_visible_fold(ptr(pix), pix.shape[0], pix.shape[1], int(min_pixels), ptr(views), ptr(pixels), _stream()),
+          "jt_visible_fold")
+
+
+def triangle_visibility(vertices, triangles, proj, H, W, min_pixels=1, cull=False, near=1e-3, views_per_call=8):
+    """Which triangles of a mesh (vertices [nv, 3] fp32, triangles [nt, 3] int32) the cameras proj [V, 3, 4] see at H x W
+    (csrc/jt_visible.hip; proj, near and cull as rasterize takes them).  Returns Opt(views [nt] int32: in how many views the
+    triangle is the nearest one at `min_pixels` pixel centres or more; pixels [nt] int64: at how many pixel centres over all
+    views; status_counts [V, 5] int64: rasterize's).
+
+    Per slab of `views_per_call` views: a z-buffer is allocated and cleared, then jt_raster_project, jt_raster_draw,
+    jt_visible_tally (the winners counted per view and triangle, integer atomics) and jt_visible_fold (into views and pixels, no
+    atomics).  No resolve: the winner is the low word of the z-buffer's key.  Everything stays on the device and nothing is read
+    back; every step is integer work on the bits jt_raster_draw leaves, so two calls return the same bits however the views are
+    batched.  A triangle is seen only where it wins a pixel CENTRE: one smaller than a pixel may win none."""
+    from .options import Opt
+    H, W, step = int(H), int(W), int(views_per_call)
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or triangles.dim() != 2 or triangles.shape[1] != 3:
+        raise ValueError("triangle_visibility: vertices are [nv, 3] and triangles [nt, 3] (got %s, %s)"
+                         % (tuple(vertices.shape), tuple(triangles.shape)))
+    if triangles.dtype != torch.int32:
+        raise ValueError("triangle_visibility: triangles are int32 vertex ids (got %s)" % triangles.dtype)
+    if proj.dim() != 3 or tuple(proj.shape[1:]) != (3, 4) or proj.shape[0] < 1:
+        raise ValueError("triangle_visibility: proj is [V, 3, 4] with V >= 1 (got %s)" % (tuple(proj.shape),))
+    if vertices.shape[0] < 1 or triangles.shape[0] < 1:
+        raise ValueError("triangle_visibility: an empty mesh (%d vertices, %d triangles)" % (vertices.shape[0], triangles.shape[0]))
+    if H < 1 or W < 1 or step < 1:
+        raise ValueError("triangle_visibility: H, W and views_per_call are at least 1 (got %d, %d, %d)" % (H, W, step))
+    if isinstance(min_pixels, bool) or int(min_pixels) != min_pixels or int(min_pixels) < 1:
+        raise ValueError("triangle_visibility: min_pixels is an integer >= 1 (got %r)" % (min_pixels,))
+    dev = vertices.device
+    vertices = vertices.detach().contiguous().float()
+    triangles = triangles.detach().contiguous()
+    proj = proj.detach().to(dev).contiguous().float()
+    nt = triangles.shape[0]
+    views = torch.zeros(nt, device=dev, dtype=torch.int32)
+    pixels = torch.zeros(nt, device=dev, dtype=torch.int64)
+    codes = torch.arange(len(RASTER_STATUS), device=dev, dtype=torch.uint8)
+    counts = []
+    for v0 in range(0, proj.shape[0], step):
+        screen = raster_project(vertices, proj[v0:v0 + step], near)
+        zbuf, status = raster_draw(screen, triangles, H, W, cull)
+        visible_fold(visible_tally(zbuf, nt), min_pixels, views, pixels)
+        counts.append(torch.stack([(status == c).sum(1) for c in codes], 1))
+    return Opt(views=views, pixels=pixels, status_counts=torch.cat(counts))
+
+
+def _triangle_mask(mask, nt, who, name):
+    if mask.dtype not in (torch.uint8, torch.bool) or tuple(mask.shape) != (nt,):
+        raise ValueError("%s: %s is uint8 (or bool) [nt] (got %s %s for %d triangles)" % (who, name, mask.dtype, tuple(mask.shape), nt))
+    return mask.detach().to(torch.uint8).contiguous()
+
+
+def grow_triangles(triangles, n_vertices, visible, rings):
+    """`visible` [nt] uint8 (or bool; non-zero: in the set) grown by `rings` rings of vertex neighbours over triangles [nt, 3]
+    int32 of a mesh of n_vertices vertices: uint8 [nt], per ring visible | (a vertex shared with a triangle of the set).  Two
+    launches per ring -- jt_visible_mark flags the vertices of the set, jt_visible_spread takes every triangle that touches a
+    flag; the step between them is a grid-wide dependency -- plain stores, no atomics, the same bits on every call.  A triangle
+    with an id outside [0, n_vertices) flags nothing and is never taken.  rings = 0 returns its input's bits."""
+    if triangles.dim() != 2 or triangles.shape[1] != 3 or triangles.dtype != torch.int32:
+        raise ValueError("grow_triangles: triangles are int32 [nt, 3] (got %s %s)" % (triangles.dtype, tuple(triangles.shape)))
+    nt, nv = triangles.shape[0], int(n_vertices)
+    visible = _triangle_mask(visible, nt, "grow_triangles", "visible")
+    if isinstance(rings, bool) or int(rings) != rings or int(rings) < 0:
+        raise ValueError("grow_triangles: rings is an integer >= 0 (got %r)" % (rings,))
+    if nv < 0:
+        raise ValueError("grow_triangles: n_vertices is not negative (got %d)" % nv)
+    cur = visible.clone()
+    if nt == 0 or nv == 0:
+        return cur
+    triangles = triangles.detach().contiguous()
+    for _ in range(int(rings)):
+        flag = torch.zeros(nv, device=triangles.device, dtype=torch.uint8)
+        out = torch.empty_like(cur)
+        check(lib.jt_visible_mark(ptr(triangles), nt, nv, ptr(cur), ptr(flag), _stream()), "jt_visible_mark")
+        check(lib.jt_visible_spread(ptr(triangles), nt, nv, ptr(cur), ptr(flag), ptr(out), _stream()), "jt_visible_spread")
+        cur = out
+    return cur
+
+
+def select_triangles(vertices, triangles, keep, normals=None, colors=None):
+    """The mesh of the triangles with keep[t] != 0 (keep [nt] uint8 or bool) and ids in range, without the vertices no kept
+    triangle names: (vertices' [nv', 3], triangles' [nt', 3] int32 with remapped ids, normals' or None, colors' or None,
+    n_dropped).  The per-triangle counterpart of compact_mesh: jt_mesh_select_count, two cumsums, ONE host read (the two
+    sizes), jt_mesh_filter_emit: triangles and vertices keep their order, two calls return the same bits.  Empty results are
+    [0, 3] tensors; an all-ones keep on a mesh without unused vertices returns the input's bits."""
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or triangles.dim() != 2 or triangles.shape[1] != 3:
+        raise ValueError("select_triangles: vertices are [nv, 3] and triangles [nt, 3] (got %s, %s)" % (tuple(vertices.shape), tuple(triangles.shape)))
+    if triangles.dtype != torch.int32:
+        raise ValueError("select_triangles: triangles are int32 vertex ids (got %s)" % triangles.dtype)
+    nv, nt = vertices.shape[0], triangles.shape[0]
+    keep = _triangle_mask(keep, nt, "select_triangles", "keep")
+    dev = vertices.device
+    vertices = vertices.detach().contiguous().float()
+    triangles = triangles.detach().contiguous()
+    attrs = []
+    for name, a in (("normals", normals), ("colors", colors)):
+        if a is not None:
+            if tuple(a.shape) != (nv, 3):
+                raise ValueError("select_triangles: %s are [nv, 3] (got %s for %d vertices)" % (name, tuple(a.shape), nv))
+            a = a.detach().contiguous().float()
+        attrs.append(a)
+    normals, colors = attrs
+
+    def empty():
+        return (vertices.new_empty(0, 3), triangles.new_empty(0, 3), None if normals is None else normals.new_empty(0, 3),
+                None if colors is None else colors.new_empty(0, 3))
+    if nv == 0 or nt == 0:
+        return empty() + (nt,)
+    kept = torch.empty(nt, device=dev, dtype=torch.uint8)
+    used = torch.zeros(nv, device=dev, dtype=torch.uint8)
+    check(lib.jt_mesh_select_count(ptr(triangles), nt, nv, ptr(keep), ptr(kept), ptr(used), _stream()), "jt_mesh_select_count")
+    vert_end = torch.cumsum(used, 0, dtype=torch.int64)
+    tri_end = torch.cumsum(kept, 0, dtype=torch.int64)
+    nv_out, nt_out = (int(v) for v in torch.stack([vert_end[-1], tri_end[-1]]).tolist())
+    if nt_out == 0:
+        return empty() + (nt,)
+    vert_offset, tri_offset = vert_end.sub_(used), tri_end.sub_(kept)
+    v_out = torch.empty(nv_out, 3, device=dev, dtype=torch.float32)
+    t_out = torch.empty(nt_out, 3, device=dev, dtype=torch.int32)
+    n_out = torch.empty(nv_out, 3, device=dev, dtype=torch.float32) if normals is not None else None
+    c_out = torch.empty(nv_out, 3, device=dev, dtype=torch.float32) if colors is not None else None
+    check(lib.jt_mesh_filter_emit(ptr(vertices), ptr(normals), ptr(colors), nv, ptr(triangles), nt, ptr(kept), ptr(used),
+                                  ptr(vert_offset), ptr(tri_offset), nv_out, nt_out, ptr(v_out), ptr(n_out), ptr(c_out), ptr(t_out),
+                                  _stream()), "jt_mesh_filter_emit")
+    return v_out, t_out, n_out, c_out, nt - nt_out
+
+
+def visible_options(visible):
+    """extract_mesh's `visible` argument checked and completed, before any work: Opt(proj [V, 3, 4], H, W, min_views, min_pixels,
+    grow, cull, ndc: None or (sx, sy, near))"""
+    from .options import Opt
+    if not isinstance(visible, dict) or any(k not in visible for k in ("proj", "H", "W")):
+        raise ValueError("visible: a dict of proj [V, 3, 4], H and W, and optionally min_views, min_pixels, grow, cull, ndc (got %r)"
+                         % (type(visible).__name__,))
+    unknown = sorted(set(visible) - {"proj", "H", "W", "min_views", "min_pixels", "grow", "cull", "ndc"})
+    if unknown:
+        raise ValueError("visible: unknown keys %s" % unknown)
+    proj = visible["proj"]
+    if not torch.is_tensor(proj) or proj.dim() != 3 or tuple(proj.shape[1:]) != (3, 4) or proj.shape[0] < 1:
+        raise ValueError("visible: proj is a [V, 3, 4] tensor with V >= 1")
+    out = Opt(proj=None, H=0, W=0, min_views=1, min_pixels=1, grow=1, cull=False, ndc=None)
+    for key, least in (("H", 1), ("W", 1), ("min_views", 1), ("min_pixels", 1), ("grow", 0)):
+        v = visible.get(key, out[key])
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or int(v) != v or int(v) < least:
+            raise ValueError("visible: %s is an integer >= %d (got %r)" % (key, least, v))
+        out[key] = int(v)
+    out.cull = bool(visible.get("cull", False))
+    ndc = visible.get("ndc", None)
+    if ndc is not None:
+        ndc = tuple(float(v) for v in ndc)
+        if len(ndc) != 3 or not all(v > 0 and math.isfinite(v) for v in ndc):
+            raise ValueError("visible: ndc is None or (sx, sy, near), three positive finite numbers (got %r)" % (visible["ndc"],))
+    out.ndc = ndc
+    dict.__setitem__(out, "proj", proj)
+    return out
+
+
+def visible_triangles(vertices, triangles, visible):
+    """The triangles of the mesh that stay under `visible` (visible_options'): (kept [nt] uint8, seen [nt] uint8).
+    seen = triangle_visibility(...).views >= min_views, kept = grow_triangles(seen, grow).  With ndc = (sx, sy, near) the vertices
+    are carried through ndc_to_world (no max_depth) FOR DRAWING ONLY -- a vertex at or beyond infinity is handed to the
+    rasteriser as NaN, so its triangles are not drawn, never seen, and taken out of `kept` again after the growth; the rings
+    are grown on the mesh's own connectivity, which the map does not change.  Nothing is read back."""
+    draw = vertices
+    drawable = None
+    if visible.ndc is not None:
+        world, _, status = ndc_to_world(vertices, *visible.ndc)
+        bad = status != 0
+        draw = torch.where(bad[:, None], torch.full_like(world, float("nan")), world)
+        ids = triangles.long().clamp(0, vertices.shape[0] - 1)
+        drawable = ~bad[ids].any(-1)
+    vis = triangle_visibility(draw, triangles, visible.proj, visible.H, visible.W, min_pixels=visible.min_pixels, cull=visible.cull)
+    seen = (vis.views >= visible.min_views).to(torch.uint8)
+    kept = grow_triangles(triangles, vertices.shape[0], seen, visible.grow)
+    if drawable is not None:
+        kept = kept * drawable.to(torch.uint8)
+    return kept, seen
+
+
 def density_gradient(cfg, density_plane, density_line, xyz, want_feat=True):
     """(feat [n] or None, grad [n, 3]) at world points xyz [n, 3]: the density feature before shift and activation and its
     world-space gradient (jt_density_gradient; the alpha mask is ignored, points beyond the box meet zero padding)."""

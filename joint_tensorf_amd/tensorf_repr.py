@@ -22,9 +22,11 @@ VEC_MODE = ops.VEC_MODE
 # normals / colors: [nv, 3] fp32 per vertex when asked for; n_components: (kept, dropped) when a component filter ran;
 # n_degenerate_normals: vertices whose density gradient was zero or non-finite (their normal is (0, 0, 0)) when normals were formed;
 # simplified: (cells, n_vertices_in, n_triangles_in, n_dropped_invalid, n_collapsed) when the mesh went through ops.simplify_mesh;
-# texture: bake_texture's Opt(atlas uint8 [H, W, 3], uv [nt, 3, 2] in pixel units, layout) when a texture was asked for
+# texture: bake_texture's Opt(atlas uint8 [H, W, 3], uv [nt, 3, 2] in pixel units, layout) when a texture was asked for;
+# visible: (n_views, H, W, min_views, min_pixels, grow, cull, n_vertices_in, n_triangles_in, n_seen, n_grown, n_dropped) when the
+# mesh was culled to what its cameras see (extract_mesh(visible=))
 Mesh = collections.namedtuple("Mesh", "vertices triangles lo hi shape level normals colors n_components n_degenerate_normals "
-                              "simplified texture", defaults=(None, None, None, None, None, None))
+                              "simplified texture visible", defaults=(None, None, None, None, None, None, None))
 
 
 def _channel_last_param(t):
@@ -422,7 +424,8 @@ class BAT_VMSplit(torch.nn.Module):
 
     @torch.no_grad()
     def extract_mesh(self, res=None, level=0.005, cap=True, slab_points=1 << 24, keep_largest=None, min_points=None,
-                     normals=False, colors=False, view_pe_progress=None, fea_pe_progress=None, simplify=None, texture=None):
+                     normals=False, colors=False, view_pe_progress=None, fea_pe_progress=None, simplify=None, texture=None,
+                     visible=None):
         """The surface {one-step opacity = level} of the field as a triangle mesh, extracted on the device (ops.mesh_from_lattice):
         a Mesh of vertices [nv, 3] fp32 in the scene box's coordinates, triangles [nt, 3] int32 with normals pointing out of the
         opaque side, and the box (lo, hi), the size (shape) and the level of the lattice the surface was taken on.  What the
@@ -446,7 +449,18 @@ class BAT_VMSplit(torch.nn.Module):
         n_dropped_invalid, n_collapsed).  None launches nothing new.
         texture: S, an integer from 4 to 64 -- Mesh.texture = bake_texture(vertices, triangles, normals, block=S), baked last, on
         the mesh as it is returned (after keep_largest / min_points and after simplify); the normals are then computed whether
-        asked for or not.  An empty mesh gets none.  None launches nothing new and leaves every other field as it was."""
+        asked for or not.  An empty mesh gets none.  None launches nothing new and leaves every other field as it was.
+        visible: dict(proj [V, 3, 4], H, W, min_views=1, min_pixels=1, grow=1, cull=False, ndc=None) -- only the surface the cameras
+        `proj` see at H x W is returned (ops.visible_triangles, csrc/jt_visible.hip): a triangle is SEEN when it is the nearest
+        one at min_pixels pixel centres or more in min_views views or more, the seen set is grown by `grow` rings of vertex
+        neighbours, and the mesh compacted to it (ops.select_triangles) -- after simplify, before colours and the texture, which
+        are then evaluated only for what is returned.  ndc = (sx, sy, near) for a camera.ndc field: the vertices are carried to
+        world space for drawing only, the mask is applied to the mesh in NDC.  Mesh.visible = (n_views, H, W, min_views,
+        min_pixels, grow, cull, n_vertices_in, n_triangles_in, n_seen, n_grown, n_dropped), n_grown + n_dropped = n_triangles_in.
+        A triangle smaller than a pixel may win no pixel centre: `grow` and a larger H x W are the remedies.  None launches
+        nothing new."""
+        if visible is not None:
+            visible = ops.visible_options(visible)             # (a ValueError for a bad option, before any work)
         if texture is not None:
             ops.texture_layout(1, texture)                     # (a ValueError for what is no block size, before any work)
         if simplify is not None:
@@ -464,6 +478,7 @@ class BAT_VMSplit(torch.nn.Module):
         nrm = col = n_bad = simplified = None
         if normals or colors or simplify is not None or texture is not None:
             nrm, n_bad = self.point_normals(vertices)
+        culled = None
         if simplify is not None:
             cells = [int(math.ceil((n - 1) / float(simplify))) for n in vol.shape]
             n_in = (int(vertices.shape[0]), int(triangles.shape[0]))
@@ -471,7 +486,20 @@ class BAT_VMSplit(torch.nn.Module):
             simplified = (tuple(cells),) + n_in + tuple(dropped)
             if normals:
                 n_bad = int((nrm == 0).all(-1).sum())
-        if colors:
+        if visible is not None:
+            n_in = (int(vertices.shape[0]), int(triangles.shape[0]))
+            n_seen = n_dropped = 0
+            if n_in[0] and n_in[1]:
+                kept, seen = ops.visible_triangles(vertices, triangles, visible)
+                n_seen = int(seen.sum())
+                vertices, triangles, nrm, _, n_dropped = ops.select_triangles(vertices, triangles, kept, normals=nrm)
+                if normals:
+                    n_bad = int((nrm == 0).all(-1).sum())
+            culled = (int(visible.proj.shape[0]), visible.H, visible.W, visible.min_views, visible.min_pixels, visible.grow,
+                      visible.cull) + n_in + (n_seen, n_in[1] - n_dropped, n_dropped)
+        if colors and culled is not None and vertices.shape[0] == 0:
+            col = vertices.new_empty(0, 3)                     # (everything was culled: nothing to shade)
+        elif colors:
             zero = (nrm == 0).all(-1, keepdim=True)
             col = self.point_colors(vertices, torch.where(zero, nrm.new_tensor([0.0, 0.0, -1.0]), -nrm), view_pe_progress,
                                     fea_pe_progress)
@@ -480,7 +508,7 @@ class BAT_VMSplit(torch.nn.Module):
             tex = self.bake_texture(vertices, triangles, nrm, block=texture, view_pe_progress=view_pe_progress,
                                     fea_pe_progress=fea_pe_progress)
         return Mesh(vertices, triangles, tuple(lo), tuple(hi), tuple(vol.shape), float(level), nrm if normals else None, col,
-                    n_components, n_bad if normals else None, simplified, tex)
+                    n_components, n_bad if normals else None, simplified, tex, culled)
 
     @torch.no_grad()
     def updateAlphaMask(self, gridSize=(200, 200, 200)):
