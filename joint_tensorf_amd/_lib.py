@@ -247,3 +247,9 @@ def ptr(t):
     if not t.is_cuda:
         raise JtError("host tensor handed to a device entry point (shape %s)" % (tuple(t.shape),))
     return t.data_ptr()
+
+
+def _stream():
+    """raw hipStream_t of torch's current stream (the fast accessor; torch.cuda.current_stream() builds a
+    Python Stream object per call, ~10 us, and the hot loop asks ~20 times per iteration)."""
+    return ctypes.c_void_p(torch._C._cuda_getCurrentRawStream(torch.cuda.current_device()))

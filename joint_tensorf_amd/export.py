@@ -23,7 +23,7 @@ per view the coverage of mesh and field, their IoU, the median depth difference,
 every triangle.  It reports; it judges nothing.  The preview needs the run's image set and a world-space scene (not
 `camera.ndc` whose mesh stays in NDC).  Without a `--preview.*` option the export writes what it always wrote, byte for byte.
 
-`--frame.space=world` carries the mesh of a `camera.ndc` scene out of NDC on the device (ops.ndc_to_world, ops.compact_mesh;
+`--frame.space=world` carries the mesh of a `camera.ndc` scene out of NDC on the device (mesh_ops.ndc_to_world, mesh_ops.compact_mesh;
 csrc/jt_mesh.hip): mesh.ply then holds LLFF geometry in the frame of the refined cameras of cameras.json (`space world`, with
 `unwarp near N sx SX sy SY` and `dropped beyond B far F` comments), and `--preview.*` draws it like any world-space mesh.
 Triangles with a vertex at or behind infinity (zn >= 1: the far cap) are dropped and counted; `--frame.max_depth=D` also drops
@@ -31,7 +31,7 @@ what lies more than D world units along the reference axis away -- forward-facin
 distances and ruin a viewer's framing.  The step needs the run's image set (sx = fx / cx, sy = fy / cy of its intrinsics).
 `--frame.space=ndc` names what an NDC export does by default; without a `--frame.*` option nothing changes.
 
-`--simplify.cell=K` (a number >= 1) simplifies the mesh on the device by vertex clustering (ops.simplify_mesh;
+`--simplify.cell=K` (a number >= 1) simplifies the mesh on the device by vertex clustering (mesh_ops.simplify_mesh;
 csrc/jt_simplify.hip): the vertices that fall into one cell of K lattice spacings -- ceil((points - 1) / K) cells per axis over
 the box of the lattice -- become ONE vertex, placed where the planes (vertex, field normal) of its members meet in the
 least-squares sense and never outside their bounding box; triangles are re-indexed and the collapsed ones dropped.  It runs in
@@ -54,7 +54,7 @@ draw and psnr_vertex_color the same cameras drawn with vertex colours.  Together
 scene it is refused: a chart that is linear in NDC is not linear in world space (perspective-correct charts are not built).
 Without a `--texture.*` option the export writes what it wrote, byte for byte.
 
-`--visible.views=N|all` writes only the surface the training cameras see (ops.visible_triangles; csrc/jt_visible.hip).  The
+`--visible.views=N|all` writes only the surface the training cameras see (mesh_ops.visible_triangles; csrc/jt_visible.hip).  The
 level set of a trained field is not one skin: behind the visible surface the field is unsupervised, and hollow interiors,
 enclosed pockets and shells are extracted like everything else -- connected to the outer surface or larger than it, so
 `--surface.keep_largest` keeps them.  The mesh is drawn from N training cameras (evenly spaced over the set, as

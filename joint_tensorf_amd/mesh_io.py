@@ -348,7 +348,7 @@ def read_cameras(path):
 
 def projection_matrices(pose, intr, size=None, image_size=None):
     """[V, 3, 4] matrices intr @ pose that take a homogeneous mesh-space point to (x w, y w, w) in pixel units -- what
-    ops.rasterize draws through -- from world-to-camera poses [V, 3, 4] ([R | t]) and intrinsics [V, 3, 3], as the views of a
+    mesh_ops.rasterize draws through -- from world-to-camera poses [V, 3, 4] ([R | t]) and intrinsics [V, 3, 3], as the views of a
     cameras.json hold them (tensors or arrays; the result is of the kind of `pose`).  size = (H, W) renders at another size
     than the image_size = (H, W) the intrinsics belong to: their first row is scaled by W / W0 and their second by H / H0, as the
     loaders rescale them when they resize an image set (datasets.py).  Pixel centres are at half-integers, as for the ray

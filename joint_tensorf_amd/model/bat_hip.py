@@ -18,7 +18,7 @@ import os
 import numpy as np
 import torch
 
-from .. import ops
+from .. import mesh_ops, ops
 from .. import tensorf_repr
 from ..options import Opt
 
@@ -1098,7 +1098,7 @@ class Model(torch.nn.Module):
         camera.ndc scene (a chart that is linear in NDC is not linear in world space): a ValueError before any work.
 
         opt.visible.views = "all" or N (absent or 0: off, nothing new is called) writes only the surface the training cameras
-        see (extract_mesh(visible=) -> ops.visible_triangles, csrc/jt_visible.hip): N views evenly spaced over the training set
+        see (extract_mesh(visible=) -> mesh_ops.visible_triangles, csrc/jt_visible.hip): N views evenly spaced over the training set
         as preview.views picks them, drawn at opt.visible.size = [H, W] (default the image set's size; the intrinsics are
         rescaled); a triangle stays when it is the nearest one at opt.visible.min_pixels (1) pixel centres or more in
         opt.visible.min_views (1) views or more, or lies within opt.visible.grow (1) rings of vertex neighbours of one that is;
@@ -1255,8 +1255,8 @@ class Model(torch.nn.Module):
 
     @torch.no_grad()
     def unwarp_mesh(self, opt, mesh):
-        """extract_mesh's Mesh of a camera.ndc scene carried to world space, the frame of the refined cameras: ops.ndc_to_world
-        (ndc_frame's map, opt.frame.max_depth) on its vertices and normals, then ops.compact_mesh -- triangles with a vertex at or
+        """extract_mesh's Mesh of a camera.ndc scene carried to world space, the frame of the refined cameras: mesh_ops.ndc_to_world
+        (ndc_frame's map, opt.frame.max_depth) on its vertices and normals, then mesh_ops.compact_mesh -- triangles with a vertex at or
         behind infinity or beyond max_depth are dropped and counted, colours travel with their vertices.  Returns (Mesh, Opt(near,
         sx, sy, n_dropped_beyond, n_dropped_far)); lo, hi and shape stay those of the NDC lattice the surface was taken on."""
         sx, sy, near = self.ndc_frame(opt)
@@ -1264,8 +1264,8 @@ class Model(torch.nn.Module):
         if mesh.vertices.shape[0] == 0:
             return mesh, frame
         max_depth = (opt.get("frame", None) or {}).get("max_depth", None)
-        world, normals, status = ops.ndc_to_world(mesh.vertices, sx, sy, near, normals=mesh.normals, max_depth=max_depth)
-        v, t, n, c, (frame.n_dropped_beyond, frame.n_dropped_far) = ops.compact_mesh(world, mesh.triangles, status, normals=normals,
+        world, normals, status = mesh_ops.ndc_to_world(mesh.vertices, sx, sy, near, normals=mesh.normals, max_depth=max_depth)
+        v, t, n, c, (frame.n_dropped_beyond, frame.n_dropped_far) = mesh_ops.compact_mesh(world, mesh.triangles, status, normals=normals,
                                                                                    colors=mesh.colors)
         return mesh._replace(vertices=v, triangles=t, normals=n, colors=c), frame
 
@@ -1275,7 +1275,7 @@ class Model(torch.nn.Module):
     @torch.no_grad()
     def preview_scene(self, opt, directory, mesh=None):
         """<directory>/preview/mesh_<idx>.png: the mesh (extract_mesh's result; extracted from opt.mesh / opt.surface when not
-        given) drawn by the device rasteriser (ops.rasterize) from opt.preview.views training cameras, evenly spaced over the set
+        given) drawn by the device rasteriser (mesh_ops.rasterize) from opt.preview.views training cameras, evenly spaced over the set
         ("all": every one), at opt.preview.size = [H, W] (default the image set's size; the intrinsics are rescaled), shaded by
         opt.preview.shade: `color` (the vertex colours; point_colors against the normal when the mesh carries none), `normal`
         (0.5 n + 0.5), `depth` (inverse depth through eval_io.normalized_invdepth) or `texture` (the mesh's atlas, Mesh.texture,
@@ -1286,7 +1286,7 @@ class Model(torch.nn.Module):
         (opacity >= 0.5), their iou, depth_abs_median (over pixels the mesh covers and the field renders with opacity >= 0.99;
         the field's depth with the `- near + 0.05` of batBase.py:150 undone; both are distances along the camera axis),
         psnr_color (shade color or texture: over pixels both cover; shade texture adds psnr_vertex_color, the same cameras drawn
-        with vertex colours, so one report shows what the texture buys) and the five triangle counts (ops.RASTER_STATUS); then the means over
+        with vertex colours, so one report shows what the texture buys) and the five triangle counts (mesh_ops.RASTER_STATUS); then the means over
         the views.  A camera.ndc scene is drawn only as a world-space mesh (opt.frame.space == "world": a given mesh is
         unwarp_mesh's, one extracted here goes through it); its render's depth is carried to the camera axis in world units
         (eval_io.ndc_render_depth) and the report gains disparity_abs_median, the median |1/d_mesh - 1/d_field| over the same pixels.  A value over an empty set of pixels is null and left out of its mean.  Nothing is judged: the tool reports.
@@ -1362,13 +1362,13 @@ class Model(torch.nn.Module):
         if shade == "texture":
             # the atlas in place of the vertex colours; with the check also the vertex colours, for psnr_vertex_color
             if attrs is not None:
-                drawn_vertex = ops.rasterize(mesh.vertices, mesh.triangles, proj, H, W, attrs=attrs, cull=bool(cfg.get("cull", False)),
+                drawn_vertex = mesh_ops.rasterize(mesh.vertices, mesh.triangles, proj, H, W, attrs=attrs, cull=bool(cfg.get("cull", False)),
                                              background=background)
             background = 1.0 if white else 0.0
-            drawn = ops.rasterize(mesh.vertices, mesh.triangles, proj, H, W, cull=bool(cfg.get("cull", False)), background=background,
+            drawn = mesh_ops.rasterize(mesh.vertices, mesh.triangles, proj, H, W, cull=bool(cfg.get("cull", False)), background=background,
                                   texture=(mesh.texture.atlas, mesh.texture.layout))
         else:
-            drawn = ops.rasterize(mesh.vertices, mesh.triangles, proj, H, W, attrs=attrs, cull=bool(cfg.get("cull", False)),
+            drawn = mesh_ops.rasterize(mesh.vertices, mesh.triangles, proj, H, W, attrs=attrs, cull=bool(cfg.get("cull", False)),
                                   background=background)
         covered = drawn.tri >= 0
         invdepth = torch.where(covered, 1 / drawn.depth, torch.zeros_like(drawn.depth))
@@ -1441,7 +1441,7 @@ class Model(torch.nn.Module):
                     # depth differences out to infinity say little: the same pixels in inverse depth
                     row["disparity_abs_median"] = (float((1 / drawn.depth[j] - 1 / depth_f)[solid].abs().median())
                                                    if int(solid.sum()) else None)
-                row["triangles"] = dict(zip(ops.RASTER_STATUS, (int(c) for c in counts[j])))
+                row["triangles"] = dict(zip(mesh_ops.RASTER_STATUS, (int(c) for c in counts[j])))
                 rows.append(row)
         finally:
             opt.H, opt.W = size0
@@ -1449,7 +1449,7 @@ class Model(torch.nn.Module):
         for key in keys:
             vals = [r[key] for r in rows if r[key] is not None]
             means[key] = sum(vals) / len(vals) if vals else None
-        means["triangles"] = {s: sum(r["triangles"][s] for r in rows) / len(rows) for s in ops.RASTER_STATUS}
+        means["triangles"] = {s: sum(r["triangles"][s] for r in rows) / len(rows) for s in mesh_ops.RASTER_STATUS}
         report = {"mesh": "mesh.ply", "cameras": "cameras.json", "size": [H, W], "shade": shade, "cull": bool(cfg.get("cull", False)),
                   "n_triangles": int(mesh.triangles.shape[0]), "views": rows, "mean": means}
         if mesh.simplified is not None:

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import _lib, ops
+from . import _lib, mesh_ops, ops
 
 MAT_MODE = ops.MAT_MODE
 VEC_MODE = ops.VEC_MODE
@@ -21,7 +21,7 @@ VEC_MODE = ops.VEC_MODE
 # what extract_mesh returns: the arrays on the device, and the lattice they were taken on (box, points per axis, iso-level)
 # normals / colors: [nv, 3] fp32 per vertex when asked for; n_components: (kept, dropped) when a component filter ran;
 # n_degenerate_normals: vertices whose density gradient was zero or non-finite (their normal is (0, 0, 0)) when normals were formed;
-# simplified: (cells, n_vertices_in, n_triangles_in, n_dropped_invalid, n_collapsed) when the mesh went through ops.simplify_mesh;
+# simplified: (cells, n_vertices_in, n_triangles_in, n_dropped_invalid, n_collapsed) when the mesh went through mesh_ops.simplify_mesh;
 # texture: bake_texture's Opt(atlas uint8 [H, W, 3], uv [nt, 3, 2] in pixel units, layout) when a texture was asked for;
 # visible: (n_views, H, W, min_views, min_pixels, grow, cull, n_vertices_in, n_triangles_in, n_seen, n_grown, n_dropped) when the
 # mesh was culled to what its cameras see (extract_mesh(visible=))
@@ -400,12 +400,12 @@ class BAT_VMSplit(torch.nn.Module):
     def bake_texture(self, vertices, triangles, normals, block=8, slab_points=1 << 20, view_pe_progress=None, fea_pe_progress=None):
         """A per-triangle texture atlas of the appearance branch for the mesh (vertices [nv, 3] fp32, triangles [nt, 3] int32,
         normals [nv, 3] fp32), baked on the device: Opt(atlas: uint8 [H, W, 3], uv: [nt, 3, 2] fp32, the corners of every chart
-        in atlas pixel units (x right, y down; mesh_io.texture_uv), layout: ops.texture_layout(nt, block)).  Blocks of `block` x
+        in atlas pixel units (x right, y down; mesh_io.texture_uv), layout: mesh_ops.texture_layout(nt, block)).  Blocks of `block` x
         `block` texels hold the charts of two triangles each (include/jt_render.h: "Texture atlas"); colour resolution is then
-        a matter of `block`, not of the vertex count.  In slabs of `slab_points` entries: ops.texture_texels (the point on the
+        a matter of `block`, not of the vertex count.  In slabs of `slab_points` entries: mesh_ops.texture_texels (the point on the
         flat triangle, seen against the interpolated normal; texels beyond the hypotenuse are extrapolated, so no dilation pass is
         needed) -> point_colors (clamped to the scene box, the blur and PE state of the last forward, as for vertex colours) ->
-        ops.texture_pack.  Slabs compose to the bits of one pass."""
+        mesh_ops.texture_pack.  Slabs compose to the bits of one pass."""
         from . import mesh_io
         from .options import Opt
         if int(slab_points) < 1:
@@ -413,20 +413,20 @@ class BAT_VMSplit(torch.nn.Module):
         if triangles.dim() != 2 or triangles.shape[1] != 3 or triangles.shape[0] < 1:
             raise ValueError("bake_texture: triangles are [nt, 3] with nt >= 1 (got %s): an empty mesh has nothing to texture"
                              % (tuple(triangles.shape),))
-        layout = ops.texture_layout(int(triangles.shape[0]), block)
+        layout = mesh_ops.texture_layout(int(triangles.shape[0]), block)
         atlas = torch.zeros(layout.height, layout.width, 3, device=vertices.device, dtype=torch.uint8)
         for start in range(0, layout.n_entries, int(slab_points)):
             count = min(int(slab_points), layout.n_entries - start)
-            xyz, dirs, valid = ops.texture_texels(vertices, triangles, normals, layout, start, count)
+            xyz, dirs, valid = mesh_ops.texture_texels(vertices, triangles, normals, layout, start, count)
             rgb = self.point_colors(xyz, dirs, view_pe_progress, fea_pe_progress, slab_points=slab_points)
-            ops.texture_pack(rgb, valid, layout, atlas, start)
+            mesh_ops.texture_pack(rgb, valid, layout, atlas, start)
         return Opt(atlas=atlas, uv=torch.from_numpy(mesh_io.texture_uv(layout)).to(vertices.device), layout=layout)
 
     @torch.no_grad()
     def extract_mesh(self, res=None, level=0.005, cap=True, slab_points=1 << 24, keep_largest=None, min_points=None,
                      normals=False, colors=False, view_pe_progress=None, fea_pe_progress=None, simplify=None, texture=None,
                      visible=None):
-        """The surface {one-step opacity = level} of the field as a triangle mesh, extracted on the device (ops.mesh_from_lattice):
+        """The surface {one-step opacity = level} of the field as a triangle mesh, extracted on the device (mesh_ops.mesh_from_lattice):
         a Mesh of vertices [nv, 3] fp32 in the scene box's coordinates, triangles [nt, 3] int32 with normals pointing out of the
         opaque side, and the box (lo, hi), the size (shape) and the level of the lattice the surface was taken on.  What the
         upstream TensoRF's --export_mesh does with getDenseAlpha and a host marching cubes.
@@ -435,12 +435,12 @@ class BAT_VMSplit(torch.nn.Module):
         slab_points), with the blur state the last forward left, as compute_alpha (a freshly restored checkpoint has none).
         cap: one layer of zeros round the lattice and the box grown by one lattice spacing per side, so that a surface reaching
         the scene box is closed there.  level = 0.005 is the upstream export's.
-        keep_largest / min_points: floaters are removed before a triangle is emitted -- ops.keep_components on the opacity
+        keep_largest / min_points: floaters are removed before a triangle is emitted -- mesh_ops.keep_components on the opacity
         lattice (before the cap: its zeros join nothing) with fill = 0; Mesh.n_components = (kept, dropped).
         normals: Mesh.normals = point_normals(vertices), Mesh.n_degenerate_normals the zero ones.  colors: Mesh.colors =
         point_colors(vertices, -normal): the surface seen head-on ((0, 0, -1) where the normal is zero); the normals are then
         computed whether asked for or not, and returned only if asked for.
-        simplify: K >= 1, the edge of a cell in lattice spacings -- the mesh goes through ops.simplify_mesh (vertex clustering,
+        simplify: K >= 1, the edge of a cell in lattice spacings -- the mesh goes through mesh_ops.simplify_mesh (vertex clustering,
         csrc/jt_simplify.hip) with ceil((shape - 1) / K) cells per axis over the box of the lattice the surface was taken on
         (the cap included): extraction, point_normals (computed whether asked for or not), the simplification, and only then
         point_colors on the SIMPLIFIED vertices against their new normals -- what the field says at the representative, not an
@@ -451,18 +451,18 @@ class BAT_VMSplit(torch.nn.Module):
         the mesh as it is returned (after keep_largest / min_points and after simplify); the normals are then computed whether
         asked for or not.  An empty mesh gets none.  None launches nothing new and leaves every other field as it was.
         visible: dict(proj [V, 3, 4], H, W, min_views=1, min_pixels=1, grow=1, cull=False, ndc=None) -- only the surface the cameras
-        `proj` see at H x W is returned (ops.visible_triangles, csrc/jt_visible.hip): a triangle is SEEN when it is the nearest
+        `proj` see at H x W is returned (mesh_ops.visible_triangles, csrc/jt_visible.hip): a triangle is SEEN when it is the nearest
         one at min_pixels pixel centres or more in min_views views or more, the seen set is grown by `grow` rings of vertex
-        neighbours, and the mesh compacted to it (ops.select_triangles) -- after simplify, before colours and the texture, which
+        neighbours, and the mesh compacted to it (mesh_ops.select_triangles) -- after simplify, before colours and the texture, which
         are then evaluated only for what is returned.  ndc = (sx, sy, near) for a camera.ndc field: the vertices are carried to
         world space for drawing only, the mask is applied to the mesh in NDC.  Mesh.visible = (n_views, H, W, min_views,
         min_pixels, grow, cull, n_vertices_in, n_triangles_in, n_seen, n_grown, n_dropped), n_grown + n_dropped = n_triangles_in.
         A triangle smaller than a pixel may win no pixel centre: `grow` and a larger H x W are the remedies.  None launches
         nothing new."""
         if visible is not None:
-            visible = ops.visible_options(visible)             # (a ValueError for a bad option, before any work)
+            visible = mesh_ops.visible_options(visible)             # (a ValueError for a bad option, before any work)
         if texture is not None:
-            ops.texture_layout(1, texture)                     # (a ValueError for what is no block size, before any work)
+            mesh_ops.texture_layout(1, texture)                     # (a ValueError for what is no block size, before any work)
         if simplify is not None:
             if isinstance(simplify, bool) or not isinstance(simplify, (int, float)) or not (math.isfinite(simplify) and simplify >= 1):
                 raise ValueError("extract_mesh: simplify is None or a finite number >= 1, in lattice spacings (got %r)" % (simplify,))
@@ -470,11 +470,11 @@ class BAT_VMSplit(torch.nn.Module):
         lo, hi = self.aabb[0].tolist(), self.aabb[1].tolist()
         n_components = None
         if keep_largest is not None or min_points is not None:
-            vol, kept, dropped = ops.keep_components(vol, level, keep_largest=keep_largest, min_points=min_points, fill=0.0)
+            vol, kept, dropped = mesh_ops.keep_components(vol, level, keep_largest=keep_largest, min_points=min_points, fill=0.0)
             n_components = (kept, dropped)
         if cap:
-            vol, lo, hi = ops.cap_lattice(vol, lo, hi)
-        vertices, triangles = ops.mesh_from_lattice(vol, level, lo, hi)
+            vol, lo, hi = mesh_ops.cap_lattice(vol, lo, hi)
+        vertices, triangles = mesh_ops.mesh_from_lattice(vol, level, lo, hi)
         nrm = col = n_bad = simplified = None
         if normals or colors or simplify is not None or texture is not None:
             nrm, n_bad = self.point_normals(vertices)
@@ -482,7 +482,7 @@ class BAT_VMSplit(torch.nn.Module):
         if simplify is not None:
             cells = [int(math.ceil((n - 1) / float(simplify))) for n in vol.shape]
             n_in = (int(vertices.shape[0]), int(triangles.shape[0]))
-            vertices, triangles, nrm, _, dropped = ops.simplify_mesh(vertices, triangles, nrm, lo, hi, cells)
+            vertices, triangles, nrm, _, dropped = mesh_ops.simplify_mesh(vertices, triangles, nrm, lo, hi, cells)
             simplified = (tuple(cells),) + n_in + tuple(dropped)
             if normals:
                 n_bad = int((nrm == 0).all(-1).sum())
@@ -490,9 +490,9 @@ class BAT_VMSplit(torch.nn.Module):
             n_in = (int(vertices.shape[0]), int(triangles.shape[0]))
             n_seen = n_dropped = 0
             if n_in[0] and n_in[1]:
-                kept, seen = ops.visible_triangles(vertices, triangles, visible)
+                kept, seen = mesh_ops.visible_triangles(vertices, triangles, visible)
                 n_seen = int(seen.sum())
-                vertices, triangles, nrm, _, n_dropped = ops.select_triangles(vertices, triangles, kept, normals=nrm)
+                vertices, triangles, nrm, _, n_dropped = mesh_ops.select_triangles(vertices, triangles, kept, normals=nrm)
                 if normals:
                     n_bad = int((nrm == 0).all(-1).sum())
             culled = (int(visible.proj.shape[0]), visible.H, visible.W, visible.min_views, visible.min_pixels, visible.grow,
