@@ -44,9 +44,11 @@ extern "C" {
  * jt_raster_project / jt_raster_draw / jt_raster_resolve, JT_RASTER_*; 1211: + jt_mesh_unwarp_ndc / jt_mesh_filter_count / jt_mesh_filter_emit,
  * JT_UNWARP_*; 1212: + jt_simplify_keys / jt_simplify_clusters / jt_simplify_triangles, JT_SIMPLIFY_*; 1213: + jt_texture_texels /
  * jt_texture_pack / jt_raster_resolve_texture, JT_TEXTURE_*; 1214: + jt_visible_tally / jt_visible_fold / jt_visible_mark /
- * jt_visible_spread / jt_mesh_select_count.  Additions bump the last two digits, anything a caller built against the old header
+ * jt_visible_spread / jt_mesh_select_count; 1215: + jt_conv_packed_floats / jt_conv_pack_weights / jt_conv2d_relu_forward /
+ * jt_maxpool_3x3s2_forward / jt_lpips_workspace_bytes / jt_lpips_feature_layout / jt_lpips_forward, JtLpipsWeights, JT_CONV_*.
+ * Additions bump the last two digits, anything a caller built against the old header
  * would get wrong bumps the hundreds). */
-#define JT_VERSION 1214
+#define JT_VERSION 1215
 
 #define JT_OK 0
 #define JT_ERR_ARG 1         /* null pointer / bad size */
@@ -862,6 +864,59 @@ int jt_visible_spread(const int32_t* triangles, long n_triangles, long n_vertice
                       uint8_t* visible_out, void* stream);
 int jt_mesh_select_count(const int32_t* triangles, long n_triangles, long n_vertices, const uint8_t* keep_in, uint8_t* keep_out,
                          uint8_t* used, void* stream);
+
+/* LPIPS with the AlexNet backbone: the `self.lpips_loss = lpips.LPIPS(net="alex")` of model/nerf.py:33 and its call
+ * `self.lpips_loss(rgb_map * 2 - 1, var.image * 2 - 1)` of model/nerf.py:551, as launches on `stream` (csrc/jt_lpips.hip).  Stock
+ * ops run the five convolutions through a vendor convolution library; here they are implicit GEMMs on the fp32-input matrix
+ * cores (v_mfma_f32_32x32x2_f32), whose result is bit for bit a k-ordered fmaf chain.
+ *
+ *   jt_conv_pack_weights: (model/nerf.py:33, the weights the package loads) w [c_out][c_in][kh][kw] fp32, torch's layout ->
+ *     packed [Kpad][c_out], K = c_in kh kw, Kpad = K rounded up to JT_CONV_K_STEP, packed[k][m] = w[m][k] with k = (ci kh + ky) kw
+ *     + kx and zero rows behind K: the K-major image the kernel reads.  Done once per weight file.  jt_conv_packed_floats = Kpad
+ *     c_out (0 for sizes below 1 or at 2^31 elements).
+ *   jt_conv2d_relu_forward: (model/nerf.py:551, one layer of the backbone) out = relu(conv2d(x, w, stride, pad) + bias), x [batch]
+ *     [c_in][h][w], out [batch][c_out][oh][ow], oh = (h + 2 pad - kh) / stride + 1.  GEMM M = c_out, N = batch oh ow (the pixels of
+ *     all pictures flattened; a tile may straddle two pictures), K as above; the operand of the activation is gathered on the
+ *     fly, taps outside the picture read as zero.  Every output element is ONE fp32 accumulator chain over k ascending from 0,
+ *     then one fp32 add of the bias, then ReLU: the same bits for every `variant` (JT_CONV_TILE_*: the workgroup's tile, channels x
+ *     pixels; AUTO picks by the layer's size), for every batch the picture is part of, and run to run.  Against the exact
+ *     result: |out - exact| <= (K + 2) 2^-24 (conv(|x|, |w|) + |bias|).  Instantiated for (kh, kw, stride, pad) = (11, 11, 4, 2),
+ *     (5, 5, 1, 2), (3, 3, 1, 1) and c_out a multiple of 32 (of 64 for JT_CONV_TILE_64X64): anything else, and an input, output
+ *     or weight tensor of 2^31 elements or more, is JT_ERR_UNSUPPORTED.
+ *   jt_maxpool_3x3s2_forward: (model/nerf.py:551, the two 3x3 stride-2 max-pools of the backbone) x [planes][h][w] -> out [planes][(h - 3) / 2 + 1][(w - 3)
+ *     / 2 + 1], floor mode, no padding; h, w >= 3.
+ *   jt_lpips_forward: (model/nerf.py:551) pred, target [n_views][3][height][width] fp32 in [0, 1] (NOT clamped: the reference
+ *     passes the render as it is) -> out [n_views] fp64 and, unless NULL, layers [n_views][5] fp64 with out[v] = the sum of
+ *     layers[v][0..4] in ascending order.  Steps: both pictures through ((2 x - 1) - shift_c) / scale_c (fp32, the order of
+ *     operations stated in csrc/jt_lpips.hip) into ONE batch of 2 n_views; conv 3->64 11x11/4/2 + ReLU; pool, conv 64->192 5x5/1/2
+ *     + ReLU; pool, conv 192->384 3x3/1/1 + ReLU; conv 384->256 + ReLU; conv 256->256 + ReLU; after each ReLU, per pixel in fp64:
+ *     n_i = sqrt(sum_c f_i^2) + 1e-10, sum_c lin_c (f0_c / n0 - f1_c / n1)^2, and the mean over the layer's pixels.  Every sum
+ *     has one order (no atomics): the same bits run to run, and a view's value does not depend on the other views.  Identical
+ *     pictures give exactly 0.  weights: a HOST struct of device pointers: conv[l] packed by jt_conv_pack_weights, bias[l]
+ *     [c_out], lin[l] [c_out] fp32 (the package's lin<l>.model.1.weight).  workspace: jt_lpips_workspace_bytes(...) bytes,
+ *     caller-provided, 256-byte aligned, overwritten; jt_lpips_feature_layout writes table[l] = {offset in floats of layer l's
+ *     features [2 n_views][C][h][w] inside the workspace (pictures 0..n_views-1 = pred), C, h, w}, l = 0..4.  Decided before any
+ *     launch: JT_ERR_ARG for a NULL pointer, a size below 1 or a short workspace; JT_ERR_UNSUPPORTED for height or width below
+ *     31 (the second pool needs 3 rows) and for any activation of the 2 n_views batch with 2^31 elements or more (workspace
+ *     bytes: 0 then). */
+#define JT_CONV_K_STEP 32
+#define JT_CONV_TILE_AUTO 0
+#define JT_CONV_TILE_64X64 1  /* 4 waves, 2 x 2 */
+#define JT_CONV_TILE_32X32 2 /* 1 wave */
+typedef struct JtLpipsWeights {
+  const float* conv[5];
+  const float* bias[5];
+  const float* lin[5];
+} JtLpipsWeights;
+size_t jt_conv_packed_floats(int c_out, int c_in, int kh, int kw);
+int jt_conv_pack_weights(const float* w, int c_out, int c_in, int kh, int kw, float* packed, void* stream);
+int jt_conv2d_relu_forward(const float* x, const float* packed, const float* bias, int batch, int c_in, int h, int w, int c_out,
+                           int kh, int kw, int stride, int pad, int variant, float* out, void* stream);
+int jt_maxpool_3x3s2_forward(const float* x, int planes, int h, int w, float* out, void* stream);
+size_t jt_lpips_workspace_bytes(int n_views, int height, int width);
+int jt_lpips_feature_layout(int n_views, int height, int width, int64_t* table);
+int jt_lpips_forward(const float* pred, const float* target, int n_views, int height, int width, const JtLpipsWeights* weights,
+                     double* out, double* layers, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -23,6 +23,7 @@ c_i = ctypes.c_int32
 JT_ACT_SOFTPLUS, JT_ACT_RELU = 0, 1
 JT_MLP_FEA, JT_MLP_WEAKVIEW = 0, 1
 JT_SHADE_SKIP_WGRAD, JT_SHADE_POSE_ONLY = 1, 2
+JT_CONV_TILE_AUTO, JT_CONV_TILE_64X64, JT_CONV_TILE_32X32 = 0, 1, 2
 
 
 class JtScene(ctypes.Structure):
@@ -56,6 +57,10 @@ class JtBlurItem(ctypes.Structure):
     _fields_ = [("in_", ctypes.c_void_p), ("out", ctypes.c_void_p), ("tmp", ctypes.c_void_p),
                 ("taps", ctypes.c_void_p), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("C", ctypes.c_int32),
                 ("n_taps", ctypes.c_int32)]
+
+
+class JtLpipsWeights(ctypes.Structure):
+    _fields_ = [("conv", ctypes.c_void_p * 5), ("bias", ctypes.c_void_p * 5), ("lin", ctypes.c_void_p * 5)]
 
 
 class JtFiniteItem(ctypes.Structure):
@@ -159,6 +164,13 @@ SIGNATURES = {
     "jt_visible_mark": (I, [P, ctypes.c_long, ctypes.c_long, P, P, P]),
     "jt_visible_spread": (I, [P, ctypes.c_long, ctypes.c_long, P, P, P, P]),
     "jt_mesh_select_count": (I, [P, ctypes.c_long, ctypes.c_long, P, P, P, P]),
+    "jt_conv_packed_floats": (ctypes.c_size_t, [I, I, I, I]),
+    "jt_conv_pack_weights": (I, [P, I, I, I, I, P, P]),
+    "jt_conv2d_relu_forward": (I, [P, P, P, I, I, I, I, I, I, I, I, I, I, P, P]),
+    "jt_maxpool_3x3s2_forward": (I, [P, I, I, I, P, P]),
+    "jt_lpips_workspace_bytes": (ctypes.c_size_t, [I, I, I]),
+    "jt_lpips_feature_layout": (I, [I, I, I, P]),
+    "jt_lpips_forward": (I, [P, P, I, I, I, P, P, P, P, ctypes.c_size_t, P]),
     "jt_blur_batch_forward": (I, [P, I, P]),
     "jt_blur_batch_backward": (I, [P, I, P]),
     "jt_factor_reg_forward": (I, [P, I, I, I, P, P]),
@@ -202,7 +214,7 @@ def fused_lib():
 # the JT_VERSION of include/jt_render.h that SIGNATURES and the struct mirrors above were written against.  A constant, not a
 # read of the header at import time: a vendored copy of the package has no include/ directory beside it (tests/test_abi.py
 # holds this number, the header's and the library's together)
-JT_ABI_VERSION = 1214
+JT_ABI_VERSION = 1215
 
 
 def header_version():

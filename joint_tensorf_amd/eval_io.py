@@ -1,8 +1,9 @@
 """The files an evaluation leaves behind (model/bat.py:255-259, model/nerf.py:530-556,568-572,619-627): quant_pose.txt, quant.txt
 and the PNGs of the rendered views.  Host code on host tensors: nothing here needs a GPU.
 
-quant.txt keeps the reference's four columns `i psnr ssim lpips`; LPIPS needs trained AlexNet weights that this build does not
-carry, so the column holds `nan`."""
+quant.txt keeps the reference's four columns `i psnr ssim lpips`.  LPIPS needs trained AlexNet weights that this repository does
+not carry: the column holds the values of ops.lpips when the run names the two weight files (eval.lpips.alexnet,
+eval.lpips.linear), `nan` otherwise."""
 import os
 import shutil
 import subprocess
@@ -66,11 +67,15 @@ def write_quant_pose(output_path, R_error, t_error):
             f.write("{} {} {}\n".format(i, float(r), float(t)))
 
 
-def write_quant(output_path, psnr_per_view, ssim_per_view):
-    """quant.txt: `i psnr ssim lpips` per held-out view (model/nerf.py:568-572), lpips = nan"""
+def write_quant(output_path, psnr_per_view, ssim_per_view, lpips_per_view=None):
+    """quant.txt: `i psnr ssim lpips` per held-out view (model/nerf.py:568-572); without `lpips_per_view` the column is nan"""
+    if lpips_per_view is None:
+        lpips_per_view = [float("nan")] * len(psnr_per_view)
+    elif len(lpips_per_view) != len(psnr_per_view):
+        raise ValueError("write_quant: %d LPIPS values for %d views" % (len(lpips_per_view), len(psnr_per_view)))
     with open(os.path.join(output_path, "quant.txt"), "w") as f:
-        for i, (p, s) in enumerate(zip(psnr_per_view, ssim_per_view)):
-            f.write("{} {} {} {}\n".format(i, float(p), float(s), float("nan")))
+        for i, (p, s, l) in enumerate(zip(psnr_per_view, ssim_per_view, lpips_per_view)):
+            f.write("{} {} {} {}\n".format(i, float(p), float(s), float(l)))
 
 
 def write_view_pngs(directory, i, rgb=None, rgb_GT=None, depth=None):

@@ -1680,7 +1680,8 @@ class Model(torch.nn.Module):
     @torch.no_grad()
     def evaluate_view(self, opt, var, eps=1e-10):
         """The per-view body of nerf.Model.evaluate_full (model/nerf.py:534-551): optional test-time pose
-        optimisation, the sliced full-image render, PSNR, and SSIM on the device (ops.ssim: csrc/jt_metrics.hip)."""
+        optimisation, the sliced full-image render, PSNR, and SSIM on the device (ops.ssim: csrc/jt_metrics.hip); with
+        opt.eval.lpips.alexnet and opt.eval.lpips.linear set, LPIPS as well (model/nerf.py:551; ops.lpips: csrc/jt_lpips.hip)."""
         from .. import eval_io
         g = self.graph
         g.eval()
@@ -1692,16 +1693,33 @@ class Model(torch.nn.Module):
         invdepth_map = invdepth.view(-1, opt.H, opt.W, 1).permute(0, 3, 1, 2)
         psnr = -10 * g.MSE_loss(rgb_map, var.image).log10().item()
         ssim = ops.ssim(rgb_map, var.image).mean().item()     # (model/nerf.py:550: one view per batch)
-        return Opt(psnr=psnr, ssim=ssim, rgb_map=rgb_map, invdepth_map=invdepth_map,
-                   invdepth_map_normalized=eval_io.normalized_invdepth(opt, invdepth_map), var=var)
+        out = Opt(psnr=psnr, ssim=ssim, rgb_map=rgb_map, invdepth_map=invdepth_map,
+                  invdepth_map_normalized=eval_io.normalized_invdepth(opt, invdepth_map), var=var)
+        weights = self.lpips_weights(opt)
+        if weights is not None:
+            out.lpips = ops.lpips(rgb_map, var.image, weights).mean().item()     # (model/nerf.py:551)
+        return out
+
+    def lpips_weights(self, opt):
+        """The LPIPS(alex) weights of opt.eval.lpips.{alexnet,linear} (model/nerf.py:33), loaded and packed once per model and
+        pair of paths; None when neither option is set, a ValueError when only one is."""
+        from .. import lpips
+        paths = lpips.paths_from_options(opt)
+        if paths is None:
+            return None
+        key = paths + (str(opt.device),)
+        if getattr(self, "_lpips_weights", (None, None))[0] != key:
+            self._lpips_weights = (key, lpips.load_weights(paths[0], paths[1], device=opt.device))
+        return self._lpips_weights[1]
 
     def evaluate_full(self, opt, test_views=None, pose_GT=None, eps=1e-10):
         """model/bat.py:241-263 + model/nerf.py:525-572: camera alignment errors, then PSNR and SSIM per held-out view.
         `test_views`: an iterable of per-view batches (idx, pose, intr, intr_inv, image); default self.test_loader, as
         in the reference's `evaluate_full(opt)`.  With an opt.output_path the reference's result files are written:
-        quant_pose.txt and quant.txt (rank 0; the LPIPS column holds nan) and test_view/{rgb,rgb_GT,depth}_<i>.png (every rank
-        its own views)."""
+        quant_pose.txt and quant.txt (rank 0; the LPIPS column holds nan unless opt.eval.lpips names the two weight files, and
+        then `lpips_per_view` and `lpips` are returned too) and test_view/{rgb,rgb_GT,depth}_<i>.png (every rank its own views)."""
         from .. import eval_io
+        with_lpips = self.lpips_weights(opt) is not None     # (only one of the two files named: an error before any render)
         if test_views is None:
             test_views = [{k: (v.to(opt.device) if torch.is_tensor(v) else v) for k, v in dict(b).items()}
                           for b in self.test_loader]
@@ -1745,21 +1763,33 @@ class Model(torch.nn.Module):
         for i, r in zip(mine, res):
             psnr[i] = r.psnr
             ssim[i] = r.ssim
+        if with_lpips:
+            lp = torch.full((len(test_views),), float("nan"), device=opt.device, dtype=torch.float64)
+            for i, r in zip(mine, res):
+                lp[i] = r.lpips
         if world > 1:
             psnr = torch.nan_to_num(psnr, nan=0.0)
             dist.all_reduce(psnr)
             ssim = torch.nan_to_num(ssim, nan=0.0)
             dist.all_reduce(ssim)
+            if with_lpips:
+                lp = torch.nan_to_num(lp, nan=0.0)
+                dist.all_reduce(lp)
         out = Opt(R_error=error.R, t_error=error.t, views=res, psnr_per_view=psnr.tolist(),
                   psnr=float(psnr.mean()) if len(test_views) else float("nan"), ssim_per_view=ssim.tolist(),
                   ssim=float(ssim.mean()) if len(test_views) else float("nan"))
+        if with_lpips:
+            out.lpips_per_view = lp.tolist()
+            out.lpips = float(lp.mean()) if len(test_views) else float("nan")
         if rank == 0:
             print("--------------------------")
             print("PSNR:  {:8.2f}".format(out.psnr))
             print("SSIM:  {:8.2f}".format(out.ssim))
+            if with_lpips:
+                print("LPIPS: {:8.2f}".format(out.lpips))
             print("--------------------------")
             if out_path:
-                eval_io.write_quant(out_path, out.psnr_per_view, out.ssim_per_view)
+                eval_io.write_quant(out_path, out.psnr_per_view, out.ssim_per_view, out.lpips_per_view if with_lpips else None)
         return out
 
     # ---- 2-D blur cache of the supervising images + edge masks ----------------------------------

@@ -1209,6 +1209,88 @@ def ssim(pred, target, return_map=False):
     return (out, smap) if return_map else out
 
 
+CONV_TILES = (_lib.JT_CONV_TILE_64X64, _lib.JT_CONV_TILE_32X32)
+
+
+def conv_pack_weights(weight):
+    """[Cout, Cin, KH, KW] fp32 on the device -> the K-major image ops.conv2d_relu reads (jt_conv_pack_weights), once per weight"""
+    if weight.dim() != 4:
+        raise ValueError("conv_pack_weights: [Cout, Cin, KH, KW] (got %s)" % (tuple(weight.shape),))
+    w = weight.detach().contiguous().float()
+    n = lib.jt_conv_packed_floats(*w.shape)
+    packed = torch.empty(max(n, 1), device=w.device, dtype=torch.float32)
+    check(lib.jt_conv_pack_weights(ptr(w), *w.shape, ptr(packed), _stream()), "jt_conv_pack_weights")
+    return packed
+
+
+def conv2d_relu(x, packed, bias, kernel, stride, pad, tile=_lib.JT_CONV_TILE_AUTO):
+    """relu(conv2d(x, w, stride, pad) + bias) of x [B, Cin, H, W] fp32 on the fp32-input matrix cores (jt_conv2d_relu_forward);
+    `packed` = conv_pack_weights(w) of a [Cout, Cin, kernel, kernel] weight, Cout = len(bias).  One accumulator chain per output
+    element: the same bits for every `tile` (CONV_TILES) and every batch a picture is part of.  Value only."""
+    if x.dim() != 4:
+        raise ValueError("conv2d_relu: x must be [B, Cin, H, W] (got %s)" % (tuple(x.shape),))
+    x = x.detach().contiguous().float()
+    B, Cin, H, W = x.shape
+    Cout = int(bias.numel())
+    if packed.numel() != lib.jt_conv_packed_floats(Cout, Cin, kernel, kernel):
+        raise ValueError("conv2d_relu: packed weights of %d floats do not belong to a [%d, %d, %d, %d] weight"
+                         % (packed.numel(), Cout, Cin, kernel, kernel))
+    oh, ow = (H + 2 * pad - kernel) // stride + 1, (W + 2 * pad - kernel) // stride + 1
+    out = torch.empty((B, Cout, max(oh, 0), max(ow, 0)), device=x.device, dtype=torch.float32)
+    check(lib.jt_conv2d_relu_forward(ptr(x), ptr(packed), ptr(bias), B, Cin, H, W, Cout, kernel, kernel, stride, pad, int(tile),
+                                     ptr(out), _stream()), "jt_conv2d_relu_forward")
+    return out
+
+
+def max_pool_3x3s2(x):
+    """F.max_pool2d(x, 3, 2) of [..., H, W] fp32 (floor mode, no padding; jt_maxpool_3x3s2_forward)"""
+    x = x.detach().contiguous().float()
+    H, W = x.shape[-2:]
+    planes = x.numel() // max(H * W, 1)
+    out = torch.empty(tuple(x.shape[:-2]) + (max((H - 3) // 2 + 1, 0), max((W - 3) // 2 + 1, 0)), device=x.device,
+                      dtype=torch.float32)
+    check(lib.jt_maxpool_3x3s2_forward(ptr(x), planes, H, W, ptr(out), _stream()), "jt_maxpool_3x3s2_forward")
+    return out
+
+
+def _lpips_run(pred, target, weights):
+    if pred.dim() != 4 or pred.shape != target.shape or pred.shape[1] != 3:
+        raise ValueError("lpips: pred and target must both be [V, 3, H, W] (got %s and %s)" % (tuple(pred.shape), tuple(target.shape)))
+    x, y = pred.detach().contiguous().float(), target.detach().contiguous().float()
+    V, _, H, W = x.shape
+    out = torch.empty(V, device=x.device, dtype=torch.float64)
+    layers = torch.empty((V, 5), device=x.device, dtype=torch.float64)
+    nbytes = lib.jt_lpips_workspace_bytes(V, H, W)
+    ws = torch.empty(max(nbytes // 4, 1), device=x.device, dtype=torch.float32)   # (the caching allocator: capturable)
+    check(lib.jt_lpips_forward(ptr(x), ptr(y), V, H, W, ctypes.byref(weights.struct(x.device)), ptr(out), ptr(layers), ptr(ws),
+                               nbytes, _stream()), "jt_lpips_forward")
+    return out, layers, ws
+
+
+def lpips(pred, target, weights, return_layers=False):
+    """LPIPS(alex) of every picture pair of a batch, pred / target [V, 3, H, W] fp32 in [0, 1]: the `self.lpips_loss(rgb_map * 2 -
+    1, var.image * 2 - 1)` of the evaluation loop (model/nerf.py:551) per view, as launches on the current stream (jt_lpips_forward;
+    no host read here).  `weights`: lpips.load_weights(...).  Nothing is clamped: the reference passes the render as it is.
+    Returns a [V] float64 tensor on the device and, with `return_layers`, the five layers' terms [V, 5] whose ascending sum it
+    is.  Value only: the reference has no LPIPS loss."""
+    out, layers, _ = _lpips_run(pred, target, weights)
+    return (out, layers) if return_layers else out
+
+
+def lpips_features(pred, target, weights):
+    """ops.lpips plus what its head read: (out [V], layers [V, 5], [five feature stacks [2V, C, h, w] fp32, pictures 0..V-1 =
+    pred]) -- views of the call's workspace, for tests and tools/lpips_bench.py"""
+    out, layers, ws = _lpips_run(pred, target, weights)
+    V, _, H, W = pred.shape
+    table = (ctypes.c_int64 * 20)()
+    check(lib.jt_lpips_feature_layout(V, H, W, table), "jt_lpips_feature_layout")
+    feats = []
+    for l in range(5):
+        off, C, h, w = (int(v) for v in table[4 * l:4 * l + 4])
+        feats.append(ws[off:off + 2 * V * C * h * w].view(2 * V, C, h, w))
+    return out, layers, feats
+
+
 _INGEST_TABLES = {}
 
 

@@ -106,7 +106,7 @@ def parse_overrides(argv):
 
 
 # top-level keys a run may set that no yaml of configs/ lists (read with opt.get by model/bat_hip.py and checkpoint.py)
-RUNTIME_KEYS = ("output_path", "load", "resume", "freq", "train_graph", "early_stop_iter", "device", "name", "group")
+RUNTIME_KEYS = ("output_path", "load", "resume", "freq", "train_graph", "early_stop_iter", "device", "name", "group", "eval")
 
 
 def apply_overrides(opt, over):
