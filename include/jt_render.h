@@ -45,10 +45,10 @@ extern "C" {
  * JT_UNWARP_*; 1212: + jt_simplify_keys / jt_simplify_clusters / jt_simplify_triangles, JT_SIMPLIFY_*; 1213: + jt_texture_texels /
  * jt_texture_pack / jt_raster_resolve_texture, JT_TEXTURE_*; 1214: + jt_visible_tally / jt_visible_fold / jt_visible_mark /
  * jt_visible_spread / jt_mesh_select_count; 1215: + jt_conv_packed_floats / jt_conv_pack_weights / jt_conv2d_relu_forward /
- * jt_maxpool_3x3s2_forward / jt_lpips_workspace_bytes / jt_lpips_feature_layout / jt_lpips_forward, JtLpipsWeights, JT_CONV_*.
- * Additions bump the last two digits, anything a caller built against the old header
+ * jt_maxpool_3x3s2_forward / jt_lpips_workspace_bytes / jt_lpips_feature_layout / jt_lpips_forward, JtLpipsWeights, JT_CONV_*;
+ * 1216: + jt_fusion_integrate / jt_fusion_finish.  Additions bump the last two digits, anything a caller built against the old header
  * would get wrong bumps the hundreds). */
-#define JT_VERSION 1215
+#define JT_VERSION 1216
 
 #define JT_OK 0
 #define JT_ERR_ARG 1         /* null pointer / bad size */
@@ -864,6 +864,38 @@ int jt_visible_spread(const int32_t* triangles, long n_triangles, long n_vertice
                       uint8_t* visible_out, void* stream);
 int jt_mesh_select_count(const int32_t* triangles, long n_triangles, long n_vertices, const uint8_t* keep_in, uint8_t* keep_out,
                          uint8_t* used, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Depth-map fusion (csrc/jt_fusion.hip): the depth maps a field RENDERS from its cameras fused into a truncated signed distance
+ * volume on the lattice jt_mesh_count / jt_mesh_emit extract.  The reference exports no geometry (it kept only the `trimesh:`
+ * option block); the maps are those of its render, batBase.py:147-150, with the background term and the offset undone by the
+ * caller.  One lane per lattice point, no atomics, no LDS; every fp32 operation is rounded on its own (no fused multiply-add), so
+ * a NumPy float32 statement of this comment reproduces the kernels bit for bit (tests/fusion_ref.py).
+ *
+ *   jt_fusion_integrate: adds the n_views views of the call, in ascending order, into the running state sum [nx][ny][nz] fp32 and
+ *     count [nx][ny][nz] int32 (z fastest; zeroed by the caller before the first call; read and written once per call, so slabs of
+ *     views compose to the bits of one call).  depth, opacity: [n_views][H][W] fp32, depth along the camera axis; proj: [n_views][3]
+ *     [4] fp32 as jt_raster_project takes it (intr @ [R|t]: the third row gives the camera-axis depth w).  lo3 / hi3 are HOST
+ *     pointers.  Per point (i, j, k) and view:
+ *       x, y, z = P_axis(index) = lo (1 - s) + hi s with s = float(index) / float(n - 1): jt_mesh_emit's lattice positions;
+ *       xw = ((p00 x + p01 y) + p02 z) + p03, left to right, likewise yw (row 1) and w (row 2);
+ *       skipped unless w > near; u = xw / w, v = yw / w; skipped unless 0 <= u < W and 0 <= v < H (a NaN fails every test);
+ *       col = (int)u, row = (int)v: the nearest pixel, centres at half-integers, no filtering;
+ *       d = depth[view][row][col], a = opacity[view][row][col]; the ray found a surface iff d is finite, d > 0 and a >=
+ *       min_opacity.  Without one: carve != 0 counts the point as seen empty (sum += 1, count += 1), carve == 0 skips the view.
+ *       With one: s = d - w; s < -trunc skips the view (the point is occluded); else t = s / trunc, 1 where t > 1; sum += t,
+ *       count += 1.
+ *   jt_fusion_finish: per point of the n: count >= min_views gives lattice = 0.5 (1 - sum / float(count)) and seen = 1, else
+ *     lattice = 0 and seen = 0 (lattice [n] fp32, seen [n] uint8).  The lattice is occupancy-like: 1 deep inside, 0 outside or
+ *     unknown, the surface at level 0.5.
+ * One launch each on `stream`, nothing else; every argument is checked before the launch.  JT_ERR_ARG for a NULL pointer, any n <
+ * 2, n_views < 0, H or W < 1, trunc not a positive finite number, a NaN min_opacity or near, min_views < 1; JT_ERR_UNSUPPORTED when
+ * nx ny nz > 2^27 or n_views H W reaches 2^31; n_views == 0 launches nothing (depth, opacity and proj may then be NULL) and is
+ * JT_OK. */
+int jt_fusion_integrate(const float* depth, const float* opacity, const float* proj, int n_views, int H, int W, int nx, int ny,
+                        int nz, const float* lo3, const float* hi3, float trunc, float min_opacity, int carve, float near,
+                        float* sum, int32_t* count, void* stream);
+int jt_fusion_finish(const float* sum, const int32_t* count, long n, int min_views, float* lattice, uint8_t* seen, void* stream);
 
 /* LPIPS with the AlexNet backbone: the `self.lpips_loss = lpips.LPIPS(net="alex")` of model/nerf.py:33 and its call
  * `self.lpips_loss(rgb_map * 2 - 1, var.image * 2 - 1)` of model/nerf.py:551, as launches on `stream` (csrc/jt_lpips.hip).  Stock

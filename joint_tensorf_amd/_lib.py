@@ -164,6 +164,8 @@ SIGNATURES = {
     "jt_visible_mark": (I, [P, ctypes.c_long, ctypes.c_long, P, P, P]),
     "jt_visible_spread": (I, [P, ctypes.c_long, ctypes.c_long, P, P, P, P]),
     "jt_mesh_select_count": (I, [P, ctypes.c_long, ctypes.c_long, P, P, P, P]),
+    "jt_fusion_integrate": (I, [P, P, P, I, I, I, I, I, I, P, P, F, F, I, F, P, P, P]),
+    "jt_fusion_finish": (I, [P, P, ctypes.c_long, I, P, P, P]),
     "jt_conv_packed_floats": (ctypes.c_size_t, [I, I, I, I]),
     "jt_conv_pack_weights": (I, [P, I, I, I, I, P, P]),
     "jt_conv2d_relu_forward": (I, [P, P, P, I, I, I, I, I, I, I, I, I, I, P, P]),
@@ -214,7 +216,7 @@ def fused_lib():
 # the JT_VERSION of include/jt_render.h that SIGNATURES and the struct mirrors above were written against.  A constant, not a
 # read of the header at import time: a vendored copy of the package has no include/ directory beside it (tests/test_abi.py
 # holds this number, the header's and the library's together)
-JT_ABI_VERSION = 1215
+JT_ABI_VERSION = 1216
 
 
 def header_version():

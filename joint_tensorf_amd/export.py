@@ -69,6 +69,22 @@ same numbers.  A triangle is seen only if it wins a pixel CENTRE: on an unsimpli
 across and may win none -- `--visible.grow` and a larger `--visible.size` are the remedies; after `--simplify.cell=4` a
 triangle is tens of pixels across.  Without a `--visible.*` option the export writes what it wrote, byte for byte.
 
+`--fusion.views=N|all` exports a second surface: not the level set of the opacity, which sits wherever the density ramp crosses
+a small threshold and carries whatever the unsupervised interior holds, but the surface of the depth maps the field RENDERS from
+its refined training cameras -- what the photometric loss shaped, and what the pose refinement made mutually consistent.  N
+training views (evenly spaced over the set, as `--visible.views` picks them) are rendered at `--fusion.size=[H,W]` (default
+data.image_size), their expected camera-axis depth (sum w z / sum w, the render's background term and offset undone) and opacity
+are fused, `--fusion.views_per_call` (8) views per launch, into a truncated signed distance volume on the `--mesh.res` lattice
+(mesh_ops.fusion_integrate; csrc/jt_fusion.hip): a lattice point is projected to its nearest pixel of every view; a ray of opacity
+below `--fusion.min_opacity` (0.5) found no surface and, with `--fusion.carve` (true), carves the point empty; the distance is
+truncated at `--fusion.trunc` (4) lattice spacings; a point that fewer than `--fusion.min_views` (1) views observed is unknown
+and no triangle of a cell with such a corner is written.  The surface is the fused lattice's level 0.5 (`--mesh.level` cannot be
+given with it); `--surface.*`, `--simplify.cell`, `--visible.*`, `--texture.block` and `--preview.*` then work on it as on the
+level set, with normals, colours and the atlas still the field's, evaluated at the fused surface.  mesh.ply gains the comment
+`fusion views V size H W trunc T min_opacity A min_views M carve C seen P unobserved D`, report.json the same numbers.  It needs the
+run's image set and a world-space scene: `camera.ndc` scenes are refused (fusing forward-facing scenes, in NDC or in world
+space, is not built).  Without a `--fusion.*` option the export writes what it wrote, byte for byte.
+
 Every other `--key.sub=value` is one of the dotted overrides of joint_tensorf_amd.train."""
 import sys
 
@@ -95,6 +111,11 @@ TEXTURE_DEFAULTS = dict(block=None)
 # data.image_size; a triangle is seen when it wins min_pixels pixel centres in min_views views; grow: rings of vertex neighbours
 # kept round the seen ones; cull: back faces are not drawn while deciding)
 VISIBLE_DEFAULTS = dict(views=0, size=None, min_views=1, min_pixels=1, grow=1, cull=False)
+# the surface fused from the depth maps the field renders (views: how many training views are rendered and fused, 0 = off, or
+# "all"; size: [H, W] they are rendered at, None = data.image_size; trunc: the truncation distance in lattice spacings;
+# min_opacity: below it a ray found no surface; min_views: observations a lattice point needs; carve: rays without a surface
+# mark the points they pass as empty; views_per_call: views per launch of the integration)
+FUSION_DEFAULTS = dict(views=0, size=None, trunc=4.0, min_opacity=0.5, min_views=1, carve=True, views_per_call=8)
 
 
 def _option_group(over, name, defaults):
@@ -122,8 +143,11 @@ def build_options(argv):
                          "[--preview.shade=color|normal|depth|texture] [--preview.check=true|false] [--preview.cull=true|false] "
                          "[--frame.space=world|ndc] [--frame.max_depth=D] [--simplify.cell=K] [--texture.block=S] "
                          "[--visible.views=N|all] [--visible.size=[H,W]] [--visible.min_views=A] [--visible.min_pixels=B] "
-                         "[--visible.grow=G] [--visible.cull=true|false] "
+                         "[--visible.grow=G] [--visible.cull=true|false] [--fusion.views=N|all] [--fusion.size=[H,W]] "
+                         "[--fusion.trunc=T] [--fusion.min_opacity=A] [--fusion.min_views=M] [--fusion.carve=true|false] "
+                         "[--fusion.views_per_call=K] "
                          "[--data.root=DIR --key.sub=value ...]")
+    level_given = isinstance(over.get("mesh", None), dict) and "level" in over["mesh"]
     mesh = _option_group(over, "mesh", MESH_DEFAULTS)
     surface = _option_group(over, "surface", SURFACE_DEFAULTS)
     preview = _option_group(over, "preview", PREVIEW_DEFAULTS)
@@ -131,6 +155,7 @@ def build_options(argv):
     simplify = _option_group(over, "simplify", SIMPLIFY_DEFAULTS)
     texture = _option_group(over, "texture", TEXTURE_DEFAULTS)
     visible = _option_group(over, "visible", VISIBLE_DEFAULTS)
+    fusion = _option_group(over, "fusion", FUSION_DEFAULTS)
     opt = apply_overrides(load_options(name), over)
     opt.mesh, opt.surface, opt.preview, opt.frame, opt.simplify = mesh, surface, preview, frame, simplify
     opt.texture = texture
@@ -138,6 +163,10 @@ def build_options(argv):
         # (absent: no opt.visible at all, and nothing new is called)
         _check_visible(visible)
         opt.visible = visible
+    if fusion != FUSION_DEFAULTS:
+        # (absent: no opt.fusion at all, and nothing new is called)
+        _check_fusion(fusion, bool(opt.camera.ndc), level_given)
+        opt.fusion = fusion
     _check_preview(preview)
     _check_simplify(simplify)
     _check_frame(frame, bool(opt.camera.ndc))
@@ -256,6 +285,45 @@ def _check_visible(visible):
                          "views with --visible.views=N or --visible.views=all")
 
 
+def _check_fusion(fusion, ndc=False, level_given=False):
+    import math
+    v = fusion.views
+    if v != "all":
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or float(v) != int(v) or int(v) < 0:
+            raise SystemExit("--fusion.views is a non-negative integer or all (got %r)" % (v,))
+        fusion.views = int(v)
+    size = fusion.size
+    if size is not None:
+        size = [size] * 2 if not isinstance(size, list) else size
+        if (len(size) != 2 or any(isinstance(s, bool) or not isinstance(s, (int, float)) or float(s) != int(s)
+                                  or not 1 <= int(s) <= PREVIEW_MAX_SIZE for s in size)):
+            raise SystemExit("--fusion.size is one integer or [H, W], each from 1 to %d (got %r)" % (PREVIEW_MAX_SIZE, fusion.size))
+        fusion.size = [int(s) for s in size]
+    t = fusion.trunc
+    if isinstance(t, bool) or not isinstance(t, (int, float)) or not math.isfinite(t) or not t > 0:
+        raise SystemExit("--fusion.trunc is a positive finite number, the truncation distance in lattice spacings (got %r)" % (t,))
+    fusion.trunc = float(t)
+    a = fusion.min_opacity
+    if isinstance(a, bool) or not isinstance(a, (int, float)) or not 0 < a <= 1:
+        raise SystemExit("--fusion.min_opacity lies in (0, 1]: the opacity from which a ray has found a surface (got %r)" % (a,))
+    fusion.min_opacity = float(a)
+    for k in ("min_views", "views_per_call"):
+        n = fusion[k]
+        if isinstance(n, bool) or not isinstance(n, (int, float)) or float(n) != int(n) or int(n) < 1:
+            raise SystemExit("--fusion.%s is an integer of at least 1 (got %r)" % (k, n))
+        fusion[k] = int(n)
+    if not isinstance(fusion.carve, bool):
+        raise SystemExit("--fusion.carve is true or false (got %r)" % (fusion.carve,))
+    if fusion.views == 0:
+        raise SystemExit("--fusion.size / trunc / min_opacity / min_views / carve / views_per_call say how the depth maps are fused: "
+                         "name the views to render with --fusion.views=N or --fusion.views=all")
+    if ndc:
+        raise SystemExit("--fusion.views is not available for camera.ndc scenes: the depth maps of a forward-facing scene are "
+                         "parameters along NDC rays, and fusing them, in NDC or in world space, is not built")
+    if level_given:
+        raise SystemExit("--mesh.level cannot be given with --fusion.views: the fused surface is the level 0.5 of the fused lattice")
+
+
 def unwarps(opt):
     """whether this export carries the mesh of an NDC scene to world space (opt.frame.space == "world" on camera.ndc)"""
     return bool(opt.camera.ndc) and (opt.get("frame", None) or {}).get("space", None) == "world"
@@ -282,6 +350,10 @@ def main(argv=None):
         # refused before any GPU work: the training cameras decide what is seen
         raise SystemExit("--visible.views needs the run's image set (--data.root=DIR, or --data.synthetic=true): its cameras "
                          "decide which triangles are seen")
+    if (opt.get("fusion", None) or {}).get("views", 0) and not has_dataset(opt):
+        # refused before any GPU work: the depth maps are rendered from the training cameras
+        raise SystemExit("--fusion.views needs the run's image set (--data.root=DIR, or --data.synthetic=true): the depth maps "
+                         "are rendered from its cameras")
     if opt.preview.views != 0:
         # refused before any GPU work: the preview draws the mesh from the cameras of cameras.json
         if not has_dataset(opt):

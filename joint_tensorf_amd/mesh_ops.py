@@ -1,5 +1,5 @@
 """The export pipeline's wrappers over the C ABI (include/jt_render.h): lattice and extraction, NDC unwarp, compaction,
-simplification, components, the rasteriser, the texture atlas and visibility.  No autograd, no training state: tensors in,
+simplification, components, the rasteriser, the texture atlas, visibility and depth-map fusion.  No autograd, no training state: tensors in,
 tensors out on torch's current stream.  `ops` re-exports every name of __all__, so `ops.X` is `mesh_ops.X`; this module never
 imports `ops`.
 """
@@ -17,7 +17,7 @@ __all__ = [
     "last_components_stats", "lattice_components", "component_sizes", "keep_components", "RASTER_STATUS", "RASTER_MAX_ATTRS",
     "raster_project", "raster_draw", "raster_resolve", "texture_layout", "texture_texels", "texture_pack", "raster_resolve_texture",
     "rasterize", "visible_tally", "visible_fold", "triangle_visibility", "grow_triangles", "select_triangles", "visible_options",
-    "visible_triangles",
+    "visible_triangles", "fusion_state", "fusion_integrate", "fusion_lattice", "fused_cells", "mesh_from_fused_lattice", "fusion_options",
 ]
 
 
@@ -753,3 +753,147 @@ def visible_triangles(vertices, triangles, visible):
     if drawable is not None:
         kept = kept * drawable.to(torch.uint8)
     return kept, seen
+
+
+# ---- depth-map fusion (include/jt_render.h: "Depth-map fusion"; csrc/jt_fusion.hip) --------------------------------------
+def _fusion_state_arg(state, who):
+    """(sum fp32 [nx, ny, nz], count int32 [nx, ny, nz]) as fusion_state makes them, checked"""
+    if not isinstance(state, (tuple, list)) or len(state) != 2:
+        raise ValueError("%s: the state is fusion_state's (sum, count)" % who)
+    acc, count = state
+    _lattice_arg(acc, who)
+    if count.dtype != torch.int32 or count.shape != acc.shape or not count.is_contiguous() or count.device != acc.device:
+        raise ValueError("%s: count is contiguous int32 of the sum's shape, on its device (got %s %s)" % (who, count.dtype, tuple(count.shape)))
+    if min(acc.shape) < 2:
+        raise ValueError("%s: at least two lattice points per axis (got %s)" % (who, tuple(acc.shape)))
+    return acc, count
+
+
+def fusion_state(shape, device):
+    """the zeroed running state of a fusion over a lattice of `shape` = (nx, ny, nz) points: (sum fp32, count int32)"""
+    shape = tuple(int(v) for v in shape)
+    if len(shape) != 3 or min(shape) < 2:
+        raise ValueError("fusion_state: shape is three point counts of at least 2 (got %r)" % (shape,))
+    return (torch.zeros(shape, device=device, dtype=torch.float32), torch.zeros(shape, device=device, dtype=torch.int32))
+
+
+def fusion_integrate(state, depth, opacity, proj, lo, hi, trunc, min_opacity=0.5, carve=True, near=1e-3):
+    """jt_fusion_integrate, one launch: the views depth, opacity [V, H, W] fp32 (camera-axis depth and accumulated opacity, as the
+    field renders them) seen through proj [V, 3, 4] (rasterize's) added, in ascending order, into `state` (fusion_state's, updated
+    in place and returned) over the lattice's box lo .. hi (three floats each).  Per lattice point and view: the point is
+    projected to its nearest pixel; where that ray found a surface (finite depth > 0, opacity >= min_opacity) the truncated
+    signed distance (depth - w) / trunc, at most 1, is added unless it is below -1 (occluded); where it found none the point is
+    counted as seen empty (distance 1) when `carve`.  trunc is in world units.  No atomics and one accumulator chain per point
+    in view order: consecutive slabs of views give the bits of one call with all of them."""
+    acc, count = _fusion_state_arg(state, "fusion_integrate")
+    lo, hi = _box_arg("fusion_integrate", lo, hi)
+    if depth.dim() != 3 or depth.shape != opacity.shape:
+        raise ValueError("fusion_integrate: depth and opacity are [V, H, W] (got %s, %s)" % (tuple(depth.shape), tuple(opacity.shape)))
+    V, H, W = depth.shape
+    if proj.dim() != 3 or tuple(proj.shape) != (V, 3, 4):
+        raise ValueError("fusion_integrate: proj is [V, 3, 4], one matrix per depth map (got %s for %d views)" % (tuple(proj.shape), V))
+    if V and (H < 1 or W < 1):
+        raise ValueError("fusion_integrate: H and W are at least 1 (got %d, %d)" % (H, W))
+    trunc, min_opacity, near = float(trunc), float(min_opacity), float(near)
+    if not (trunc > 0 and math.isfinite(trunc)):
+        raise ValueError("fusion_integrate: trunc is a positive finite number, in world units (got %r)" % (trunc,))
+    if math.isnan(min_opacity) or math.isnan(near):
+        raise ValueError("fusion_integrate: min_opacity and near are numbers (got %r, %r)" % (min_opacity, near))
+    if V == 0:
+        return state
+    dev = acc.device
+    depth, opacity = depth.detach().to(dev).contiguous().float(), opacity.detach().to(dev).contiguous().float()
+    proj = proj.detach().to(dev).contiguous().float()
+    nx, ny, nz = acc.shape
+    check(lib.jt_fusion_integrate(ptr(depth), ptr(opacity), ptr(proj), V, H, W, nx, ny, nz, (ctypes.c_float * 3)(*lo),
+                                  (ctypes.c_float * 3)(*hi), trunc, min_opacity, int(bool(carve)), near, ptr(acc), ptr(count), _stream()),
+          "jt_fusion_integrate")
+    return state
+
+
+def fusion_lattice(state, min_views=1):
+    """jt_fusion_finish, one launch: (lattice [nx, ny, nz] fp32, seen [nx, ny, nz] uint8) of a fusion state -- where at least
+    min_views views observed the point, 0.5 (1 - mean truncated distance) and 1, else 0 and 0.  Occupancy-like: 1 deep inside, 0
+    outside or unknown, the surface at level 0.5."""
+    acc, count = _fusion_state_arg(state, "fusion_lattice")
+    if isinstance(min_views, bool) or int(min_views) != min_views or int(min_views) < 1:
+        raise ValueError("fusion_lattice: min_views is an integer >= 1 (got %r)" % (min_views,))
+    lattice = torch.empty_like(acc)
+    seen = torch.empty(acc.shape, device=acc.device, dtype=torch.uint8)
+    check(lib.jt_fusion_finish(ptr(acc), ptr(count), acc.numel(), int(min_views), ptr(lattice), ptr(seen), _stream()), "jt_fusion_finish")
+    return lattice, seen
+
+
+def fused_cells(seen):
+    """uint8 [nx, ny, nz]: 1 at the minimum corner of every lattice cell whose eight corners are all seen (slices of `seen`, no
+    index tensor), 0 elsewhere and where no cell begins"""
+    s = seen != 0
+    cells = torch.zeros(seen.shape, device=seen.device, dtype=torch.uint8)
+    cells[:-1, :-1, :-1] = (s[:-1, :-1, :-1] & s[1:, :-1, :-1] & s[:-1, 1:, :-1] & s[1:, 1:, :-1]
+                            & s[:-1, :-1, 1:] & s[1:, :-1, 1:] & s[:-1, 1:, 1:] & s[1:, 1:, 1:]).to(torch.uint8)
+    return cells
+
+
+def mesh_from_fused_lattice(vol, seen, level, lo, hi):
+    """mesh_from_lattice for a fused lattice (fusion_lattice's vol and seen, both [nx, ny, nz]): the iso-surface {vol = level}
+    without the triangles no depth map supports.  An unobserved point is 0, so next to a point of the truncation band it would
+    grow a sheet -- the back of every band, walls at silhouettes.  A triangle stays iff all eight corners of its OWNER cell are
+    seen: jt_mesh_count's tri_count[p] triangles of the cell with minimum corner p start at tri_offset[p], so fused_cells(seen)
+    repeated tri_count times is the per-triangle mask, compacted by select_triangles.  No geometry test looks at a position.
+    Returns (vertices [nv, 3] fp32, triangles [nt, 3] int32, (n_triangles_emitted, n_triangles_unobserved)); two calls return
+    the same bits."""
+    lo, hi = _box_arg("mesh_from_fused_lattice", lo, hi)
+    vol = vol.detach().contiguous()
+    _lattice_arg(vol, "mesh_from_fused_lattice")
+    if seen.shape != vol.shape or seen.dtype not in (torch.uint8, torch.bool):
+        raise ValueError("mesh_from_fused_lattice: seen is uint8 (or bool) of the lattice's shape (got %s %s for %s)"
+                         % (seen.dtype, tuple(seen.shape), tuple(vol.shape)))
+    flags, tris = mesh_count(vol, level)
+    vert_offset, tri_offset, totals = mesh_offsets(flags, tris)
+    nv, nt = (int(v) for v in totals.tolist())
+    vertices, triangles = mesh_emit(vol, level, lo, hi, flags, vert_offset, tri_offset, nv, nt)
+    if nt == 0:
+        return vertices, triangles, (0, 0)
+    keep = torch.repeat_interleave(fused_cells(seen).view(-1), tris.long(), output_size=nt)
+    vertices, triangles, _, _, n_dropped = select_triangles(vertices, triangles, keep)
+    return vertices, triangles, (nt - n_dropped, n_dropped)
+
+
+def fusion_options(fusion):
+    """extract_mesh's `fusion` argument checked and completed, before any work: Opt(slabs: an iterable of (depth [V, H, W], opacity
+    [V, H, W], proj [V, 3, 4]), H, W, trunc (lattice spacings), min_opacity, min_views, carve)"""
+    from .options import Opt
+    known = {"depth", "opacity", "proj", "slabs", "H", "W", "trunc", "min_opacity", "min_views", "carve"}
+    if not isinstance(fusion, dict) or any(k not in fusion for k in ("H", "W")):
+        raise ValueError("fusion: a dict of depth [V, H, W], opacity [V, H, W] and proj [V, 3, 4] (or slabs: an iterable of such "
+                         "triples), H and W, and optionally trunc, min_opacity, min_views, carve (got %r)" % (type(fusion).__name__,))
+    unknown = sorted(set(fusion) - known)
+    if unknown:
+        raise ValueError("fusion: unknown keys %s" % unknown)
+    whole = [k for k in ("depth", "opacity", "proj") if fusion.get(k, None) is not None]
+    if (fusion.get("slabs", None) is None) == (len(whole) == 0) or len(whole) not in (0, 3):
+        raise ValueError("fusion: either depth, opacity and proj, or slabs (an iterable of (depth, opacity, proj))")
+    out = Opt(slabs=None, H=0, W=0, trunc=4.0, min_opacity=0.5, min_views=1, carve=True)
+    for key in ("H", "W", "min_views"):
+        v = fusion.get(key, out[key])
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or int(v) != v or int(v) < 1:
+            raise ValueError("fusion: %s is an integer >= 1 (got %r)" % (key, v))
+        out[key] = int(v)
+    t = fusion.get("trunc", out.trunc)
+    if isinstance(t, bool) or not isinstance(t, (int, float)) or not (t > 0 and math.isfinite(t)):
+        raise ValueError("fusion: trunc is a positive finite number of lattice spacings (got %r)" % (t,))
+    a = fusion.get("min_opacity", out.min_opacity)
+    if isinstance(a, bool) or not isinstance(a, (int, float)) or not 0 < a <= 1:
+        raise ValueError("fusion: min_opacity lies in (0, 1] (got %r)" % (a,))
+    out.trunc, out.min_opacity, out.carve = float(t), float(a), bool(fusion.get("carve", True))
+    slabs = fusion.get("slabs", None)
+    if slabs is None:
+        depth, opacity, proj = (fusion[k] for k in ("depth", "opacity", "proj"))
+        if not all(torch.is_tensor(x) for x in (depth, opacity, proj)):
+            raise ValueError("fusion: depth, opacity and proj are tensors")
+        if depth.dim() != 3 or tuple(depth.shape[1:]) != (out.H, out.W) or depth.shape != opacity.shape or tuple(proj.shape) != (depth.shape[0], 3, 4):
+            raise ValueError("fusion: depth and opacity are [V, H, W] = [V, %d, %d] and proj [V, 3, 4] (got %s, %s, %s)"
+                             % (out.H, out.W, tuple(depth.shape), tuple(opacity.shape), tuple(proj.shape)))
+        slabs = [(depth, opacity, proj)]
+    dict.__setitem__(out, "slabs", slabs)
+    return out

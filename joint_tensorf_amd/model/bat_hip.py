@@ -1106,10 +1106,19 @@ class Model(torch.nn.Module):
         the vertices are carried to world space (ndc_frame's map) for drawing only, so it combines with texture.block there and
         with frame.space = world.  Needs the training set: without one a ValueError before any work.  The PLY gains the comment
         `visible views V size H W min_views A min_pixels B grow G cull C from NV NT seen S grown G2 dropped D` and the result
-        `visible` = Mesh.visible, which report.json repeats."""
+        `visible` = Mesh.visible, which report.json repeats.
+
+        opt.fusion.views = "all" or N (absent or 0: off, nothing new is called) takes the surface not from the opacity's level
+        set but from the depth maps the field renders at N training cameras (fusion_arg -> extract_mesh(fusion=) -> mesh_ops.
+        fusion_integrate, csrc/jt_fusion.hip): fused at opt.fusion.size into a truncated signed distance volume on the opt.mesh.res
+        lattice and extracted at its level 0.5 (opt.mesh.level is then not passed on); every other stage runs on it unchanged.
+        Needs the training set and a scene that is not camera.ndc: otherwise a ValueError before any work.  The PLY gains the
+        comment `fusion views V size H W trunc T min_opacity A min_views M carve C seen P unobserved D` and the result `fused` =
+        Mesh.fused, which report.json repeats."""
         from .. import eval_io, mesh_io
         mcfg = opt.get("mesh", None) or {}
         unwarp = self.unwarps(opt)
+        self.check_fusion(opt, "export_scene")
         if self.visible_views(opt) and self.train_data is None:
             raise ValueError("export_scene: visible.views needs the training set (its cameras decide what is seen)")
         block = (opt.get("texture", None) or {}).get("block", None)
@@ -1136,11 +1145,12 @@ class Model(torch.nn.Module):
             # the schedule's PE masks at the model's progress, as render_rays hands them to a forward
             for key, name in (("view_pe_progress", "c2f_view_pe_schedule"), ("fea_pe_progress", "c2f_fea_pe_schedule")):
                 pe[key] = interp_schedule(nerf.progress_host, opt[name]) if _has(opt, name) else 1.0
-        mesh = nerf.tensorf.extract_mesh(res=mcfg.get("res", None), level=float(mcfg.get("level", 0.005)),
+        fusion = self.fusion_arg(opt)
+        mesh = nerf.tensorf.extract_mesh(res=mcfg.get("res", None), **({} if fusion else {"level": float(mcfg.get("level", 0.005))}),
                                          cap=bool(mcfg.get("cap", True)), keep_largest=scfg.get("keep_largest", None),
                                          min_points=scfg.get("min_points", None), normals=ext_normals, colors=ext_colors,
                                          simplify=(opt.get("simplify", None) or {}).get("cell", None), **pe,
-                                         **({} if block is None else {"texture": block}), **self.visible_arg(opt))
+                                         **({} if block is None else {"texture": block}), **self.visible_arg(opt), **fusion)
         if block is not None and mesh.texture is None:
             raise ValueError("export_scene: the mesh is empty (level %r): nothing to texture" % (mesh.level,))
         frame = None
@@ -1162,6 +1172,9 @@ class Model(torch.nn.Module):
             out.visible = mesh.visible
             comments.append("visible views %d size %d %d min_views %d min_pixels %d grow %d cull %d from %d %d seen %d grown %d "
                             "dropped %d" % tuple(int(v) for v in mesh.visible))
+        if mesh.fused is not None:
+            out.fused = mesh.fused
+            comments.append(self.fusion_comment(mesh.fused))
         if frame is not None:
             out.unwarp = frame
             comments.append("unwarp near %r sx %r sy %r" % (frame.near, frame.sx, frame.sy))
@@ -1213,6 +1226,97 @@ class Model(torch.nn.Module):
         if isinstance(views, bool) or views is None or int(views) != views or int(views) < 0:
             raise ValueError("visible.views is all or a count (got %r)" % (views,))
         return int(views)
+
+    @staticmethod
+    def fusion_views(opt):
+        """opt.fusion.views: "all", a positive count, or 0 when the surface is not fused from rendered depth maps"""
+        views = (opt.get("fusion", None) or {}).get("views", 0)
+        if views == "all":
+            return views
+        if isinstance(views, bool) or views is None or int(views) != views or int(views) < 0:
+            raise ValueError("fusion.views is all or a count (got %r)" % (views,))
+        return int(views)
+
+    @staticmethod
+    def fusion_comment(fused):
+        """the PLY comment of Mesh.fused"""
+        return ("fusion views %d size %d %d trunc %g min_opacity %g min_views %d carve %d seen %d unobserved %d"
+                % (fused[0], fused[1], fused[2], fused[3], fused[4], fused[5], int(fused[6]), fused[7], fused[9]))
+
+    def check_fusion(self, opt, who):
+        """opt.fusion refused where it cannot run, before any work: no training set, a camera.ndc scene, a bad threshold"""
+        if not self.fusion_views(opt):
+            return
+        cfg = opt.fusion
+        if self.train_data is None:
+            raise ValueError("%s: fusion.views needs the training set (the depth maps are rendered from its cameras)" % who)
+        if opt.camera.ndc:
+            raise ValueError("%s: fusion.views is not available for camera.ndc scenes: the depth maps of a forward-facing scene "
+                             "are parameters along NDC rays, and fusing them, in NDC or in world space, is not built" % who)
+        trunc, min_views, min_opacity = cfg.get("trunc", 4.0), cfg.get("min_views", 1), cfg.get("min_opacity", 0.5)
+        if not (trunc > 0 and math.isfinite(trunc)):
+            raise ValueError("%s: fusion.trunc is a positive finite number of lattice spacings (got %r)" % (who, trunc))
+        if int(min_views) != min_views or min_views < 1:
+            raise ValueError("%s: fusion.min_views is an integer of at least 1 (got %r)" % (who, min_views))
+        if not 0 < min_opacity <= 1:
+            raise ValueError("%s: fusion.min_opacity lies in (0, 1] (got %r)" % (who, min_opacity))
+        if int(cfg.get("views_per_call", 8)) < 1:
+            raise ValueError("%s: fusion.views_per_call is at least 1 (got %r)" % (who, cfg.get("views_per_call", 8)))
+
+    @torch.no_grad()
+    def fusion_depth(self, opt, pose, intr, intr_inv, H, W):
+        """(depth [H, W], opacity [H, W]) of the field rendered at one camera (pose [1, 3, 4], intr / intr_inv [1, 3, 3] of an H x W
+        picture; opt.H / opt.W are set for the render and put back): the expected camera-axis depth sum w z / sum w.  The sample
+        parameter z is the depth along the camera's axis -- a ray direction is K^-1 (x, y, 1) rotated to the world
+        (camera.py:231-261), its camera-frame third component 1 --, and the render returns sum w z + (1 - sum w) ray_z - near + 0.05
+        (batBase.py:147-150): the background term and the offset are undone here.  0 where the opacity is 0."""
+        size0 = (opt.H, opt.W)
+        try:
+            opt.H, opt.W = H, W
+            ret = self.graph.render_by_slices(opt, pose, intr_inv=intr_inv, intr=intr)
+        finally:
+            opt.H, opt.W = size0
+        opacity = ret.opacity.view(H, W)
+        pixels = torch.arange(H * W, device=pose.device)
+        _, ray = ops.ray_gen(pose, intr_inv, intr, pixels, W, ndc=False)
+        near = float(self.graph.nerf.tensorf.near_far[0])                    # (the near plane this render marched from)
+        swz = ret.depth.view(H, W) + near - 0.05 - (1 - opacity) * ray[0, :, 2].view(H, W)
+        return torch.where(opacity > 0, swz / opacity, torch.zeros_like(swz)), opacity
+
+    @torch.no_grad()
+    def fusion_arg(self, opt):
+        """{} or {"fusion": ...} for extract_mesh from opt.fusion: the training cameras to fuse (refined, in the frame of the mesh;
+        evenly spaced over the set as visible_arg picks them) as projection matrices at opt.fusion.size with the intrinsics
+        rescaled as preview_scene rescales them, and `slabs`: a generator that renders opt.fusion.views_per_call views at a time
+        (fusion_depth, eval mode) -- extract_mesh consumes a slab before the next is rendered, so all views never live at once"""
+        views = self.fusion_views(opt)
+        if not views:
+            return {}
+        from .. import mesh_io
+        self.check_fusion(opt, "fusion_arg")
+        cfg = opt.fusion
+        pose, _ = self.get_all_training_poses(opt)
+        n = int(pose.shape[0])
+        k = n if views == "all" else min(views, n)
+        idx = sorted(set(int(round(i * (n - 1) / max(k - 1, 1))) for i in range(k)))
+        H, W = (int(v) for v in (cfg.get("size", None) or (opt.H, opt.W)))
+        pose = pose[idx].contiguous()
+        intr = self.train_data.all.intr[idx].to(pose.device, torch.float32)
+        proj = mesh_io.projection_matrices(pose, intr, size=(H, W), image_size=(opt.H, opt.W))
+        intr_s = intr.clone()
+        intr_s[:, 0] *= W / opt.W
+        intr_s[:, 1] *= H / opt.H
+        intr_inv = torch.linalg.inv(intr_s)
+        step = int(cfg.get("views_per_call", 8))
+
+        def slabs():
+            self.graph.eval()
+            for v0 in range(0, len(idx), step):
+                maps = [self.fusion_depth(opt, pose[j:j + 1], intr_s[j:j + 1], intr_inv[j:j + 1], H, W)
+                        for j in range(v0, min(v0 + step, len(idx)))]
+                yield torch.stack([m[0] for m in maps]), torch.stack([m[1] for m in maps]), proj[v0:v0 + step]
+        return {"fusion": dict(slabs=slabs(), H=H, W=W, trunc=float(cfg.get("trunc", 4.0)), min_opacity=float(cfg.get("min_opacity", 0.5)),
+                               min_views=int(cfg.get("min_views", 1)), carve=bool(cfg.get("carve", True)))}
 
     @torch.no_grad()
     def visible_arg(self, opt):
@@ -1320,10 +1424,12 @@ class Model(torch.nn.Module):
                 if shade == "color" and getattr(nerf, "progress_host", None) is not None:
                     for key, name in (("view_pe_progress", "c2f_view_pe_schedule"), ("fea_pe_progress", "c2f_fea_pe_schedule")):
                         extra[key] = interp_schedule(nerf.progress_host, opt[name]) if _has(opt, name) else 1.0
-            mesh = tf.extract_mesh(res=mcfg.get("res", None), level=float(mcfg.get("level", 0.005)), cap=bool(mcfg.get("cap", True)),
+            fusion = self.fusion_arg(opt)
+            mesh = tf.extract_mesh(res=mcfg.get("res", None), **({} if fusion else {"level": float(mcfg.get("level", 0.005))}),
+                                   cap=bool(mcfg.get("cap", True)),
                                    keep_largest=scfg.get("keep_largest", None), min_points=scfg.get("min_points", None),
                                    simplify=(opt.get("simplify", None) or {}).get("cell", None), **extra,
-                                   **({"texture": block} if shade == "texture" else {}), **self.visible_arg(opt))
+                                   **({"texture": block} if shade == "texture" else {}), **self.visible_arg(opt), **fusion)
             if unwarp:
                 mesh = self.unwarp_mesh(opt, mesh)[0]
         if shade == "texture" and mesh.triangles.shape[0] and mesh.texture is None:
@@ -1456,6 +1562,8 @@ class Model(torch.nn.Module):
             report["simplified"] = [list(mesh.simplified[0])] + [int(v) for v in mesh.simplified[1:]]
         if mesh.visible is not None:
             report["visible"] = [int(v) for v in mesh.visible]
+        if mesh.fused is not None:
+            report["fused"] = [int(v) if float(v) == int(v) else float(v) for v in mesh.fused]
         if mesh.texture is not None:
             lay = mesh.texture.layout
             report["texture"] = {"block": lay.block, "atlas": [lay.width, lay.height], "file": "atlas.png"}

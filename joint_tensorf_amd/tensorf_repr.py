@@ -24,9 +24,11 @@ VEC_MODE = ops.VEC_MODE
 # simplified: (cells, n_vertices_in, n_triangles_in, n_dropped_invalid, n_collapsed) when the mesh went through mesh_ops.simplify_mesh;
 # texture: bake_texture's Opt(atlas uint8 [H, W, 3], uv [nt, 3, 2] in pixel units, layout) when a texture was asked for;
 # visible: (n_views, H, W, min_views, min_pixels, grow, cull, n_vertices_in, n_triangles_in, n_seen, n_grown, n_dropped) when the
-# mesh was culled to what its cameras see (extract_mesh(visible=))
+# mesh was culled to what its cameras see (extract_mesh(visible=));
+# fused: (n_views, H, W, trunc, min_opacity, min_views, carve, n_points_seen, n_triangles_emitted, n_triangles_unobserved) when the
+# surface is that of the depth maps the field renders, fused on the lattice (extract_mesh(fusion=))
 Mesh = collections.namedtuple("Mesh", "vertices triangles lo hi shape level normals colors n_components n_degenerate_normals "
-                              "simplified texture visible", defaults=(None, None, None, None, None, None, None))
+                              "simplified texture visible fused", defaults=(None, None, None, None, None, None, None, None))
 
 
 def _channel_last_param(t):
@@ -423,9 +425,9 @@ class BAT_VMSplit(torch.nn.Module):
         return Opt(atlas=atlas, uv=torch.from_numpy(mesh_io.texture_uv(layout)).to(vertices.device), layout=layout)
 
     @torch.no_grad()
-    def extract_mesh(self, res=None, level=0.005, cap=True, slab_points=1 << 24, keep_largest=None, min_points=None,
+    def extract_mesh(self, res=None, level=None, cap=True, slab_points=1 << 24, keep_largest=None, min_points=None,
                      normals=False, colors=False, view_pe_progress=None, fea_pe_progress=None, simplify=None, texture=None,
-                     visible=None):
+                     visible=None, fusion=None):
         """The surface {one-step opacity = level} of the field as a triangle mesh, extracted on the device (mesh_ops.mesh_from_lattice):
         a Mesh of vertices [nv, 3] fp32 in the scene box's coordinates, triangles [nt, 3] int32 with normals pointing out of the
         opaque side, and the box (lo, hi), the size (shape) and the level of the lattice the surface was taken on.  What the
@@ -434,7 +436,7 @@ class BAT_VMSplit(torch.nn.Module):
         res: None (the factor grid), an int or three -- lattice points per axis; the lattice is dense_alpha_lattice(res,
         slab_points), with the blur state the last forward left, as compute_alpha (a freshly restored checkpoint has none).
         cap: one layer of zeros round the lattice and the box grown by one lattice spacing per side, so that a surface reaching
-        the scene box is closed there.  level = 0.005 is the upstream export's.
+        the scene box is closed there.  level = None is 0.005, the upstream export's.
         keep_largest / min_points: floaters are removed before a triangle is emitted -- mesh_ops.keep_components on the opacity
         lattice (before the cap: its zeros join nothing) with fill = 0; Mesh.n_components = (kept, dropped).
         normals: Mesh.normals = point_normals(vertices), Mesh.n_degenerate_normals the zero ones.  colors: Mesh.colors =
@@ -458,7 +460,25 @@ class BAT_VMSplit(torch.nn.Module):
         world space for drawing only, the mask is applied to the mesh in NDC.  Mesh.visible = (n_views, H, W, min_views,
         min_pixels, grow, cull, n_vertices_in, n_triangles_in, n_seen, n_grown, n_dropped), n_grown + n_dropped = n_triangles_in.
         A triangle smaller than a pixel may win no pixel centre: `grow` and a larger H x W are the remedies.  None launches
-        nothing new."""
+        nothing new.
+        fusion: dict(depth [V, H, W], opacity [V, H, W], proj [V, 3, 4], H, W, trunc=4, min_opacity=0.5, min_views=1, carve=True),
+        or with slabs = an iterable of (depth, opacity, proj) in place of the three, consumed one at a time so that all views need
+        not live at once -- the surface is not the level set of the opacity but that of the depth maps the field RENDERS (camera-
+        axis depth and accumulated opacity per pixel, through the cameras `proj` in the frame of the box), fused into a truncated
+        signed distance volume on the same `res` lattice over the scene box (mesh_ops.fusion_integrate per slab, mesh_ops.
+        fusion_lattice; csrc/jt_fusion.hip): what the photometric loss shaped, not wherever the density ramp crosses a small
+        threshold.  trunc is in lattice spacings (of the mean spacing of the three axes).  The level is then 0.5 and passing one
+        is a ValueError; keep_largest / min_points act on the fused lattice; a triangle whose cell has a corner that fewer than
+        min_views views observed is not emitted (mesh_ops.mesh_from_fused_lattice; the cap's points count as observed); every later
+        stage -- normals (the field's, at the fused vertices), simplify, visible, colours, texture -- is untouched.  Mesh.fused =
+        (n_views, H, W, trunc, min_opacity, min_views, carve, n_points_seen, n_triangles_emitted, n_triangles_unobserved).  None
+        launches nothing new."""
+        if fusion is not None:
+            if level is not None:
+                raise ValueError("extract_mesh: with fusion the surface is the fused lattice's level 0.5: level cannot be given (got %r)"
+                                 % (level,))
+            fusion = mesh_ops.fusion_options(fusion)                # (a ValueError for a bad option, before any work)
+        level = 0.005 if level is None else level
         if visible is not None:
             visible = mesh_ops.visible_options(visible)             # (a ValueError for a bad option, before any work)
         if texture is not None:
@@ -466,15 +486,28 @@ class BAT_VMSplit(torch.nn.Module):
         if simplify is not None:
             if isinstance(simplify, bool) or not isinstance(simplify, (int, float)) or not (math.isfinite(simplify) and simplify >= 1):
                 raise ValueError("extract_mesh: simplify is None or a finite number >= 1, in lattice spacings (got %r)" % (simplify,))
-        vol = self.dense_alpha_lattice(res, slab_points)
         lo, hi = self.aabb[0].tolist(), self.aabb[1].tolist()
+        seen = fused = None
+        if fusion is not None:
+            level = 0.5
+            vol, seen, n_fused_views = self.fused_lattice(res, fusion)
+        else:
+            vol = self.dense_alpha_lattice(res, slab_points)
         n_components = None
         if keep_largest is not None or min_points is not None:
             vol, kept, dropped = mesh_ops.keep_components(vol, level, keep_largest=keep_largest, min_points=min_points, fill=0.0)
             n_components = (kept, dropped)
         if cap:
             vol, lo, hi = mesh_ops.cap_lattice(vol, lo, hi)
-        vertices, triangles = mesh_ops.mesh_from_lattice(vol, level, lo, hi)
+        if fusion is not None:
+            n_seen = seen.sum()
+            if cap:
+                seen = torch.nn.functional.pad(seen, (1, 1, 1, 1, 1, 1), value=1)       # (the cap's points count as observed)
+            vertices, triangles, n_tris = mesh_ops.mesh_from_fused_lattice(vol, seen, level, lo, hi)
+            fused = (n_fused_views, fusion.H, fusion.W, fusion.trunc, fusion.min_opacity, fusion.min_views, fusion.carve,
+                     int(n_seen)) + n_tris
+        else:
+            vertices, triangles = mesh_ops.mesh_from_lattice(vol, level, lo, hi)
         nrm = col = n_bad = simplified = None
         if normals or colors or simplify is not None or texture is not None:
             nrm, n_bad = self.point_normals(vertices)
@@ -508,7 +541,27 @@ class BAT_VMSplit(torch.nn.Module):
             tex = self.bake_texture(vertices, triangles, nrm, block=texture, view_pe_progress=view_pe_progress,
                                     fea_pe_progress=fea_pe_progress)
         return Mesh(vertices, triangles, tuple(lo), tuple(hi), tuple(vol.shape), float(level), nrm if normals else None, col,
-                    n_components, n_bad if normals else None, simplified, tex, culled)
+                    n_components, n_bad if normals else None, simplified, tex, culled, fused)
+
+    @torch.no_grad()
+    def fused_lattice(self, res, fusion):
+        """(lattice [nx, ny, nz] fp32, seen [nx, ny, nz] uint8, n_views) of `fusion` (mesh_ops.fusion_options') on the `res` lattice
+        over the scene box: a zeroed state, mesh_ops.fusion_integrate per slab in the order given, mesh_ops.fusion_lattice.  The
+        truncation distance is fusion.trunc times the mean lattice spacing of the three axes."""
+        n = self._mesh_resolution(res, self.gridSize.tolist())
+        if min(n) < 2:
+            raise ValueError("extract_mesh: at least two lattice points per axis (got %r)" % (n,))
+        lo, hi = self.aabb[0].tolist(), self.aabb[1].tolist()
+        trunc = fusion.trunc * sum((hi[a] - lo[a]) / (n[a] - 1) for a in range(3)) / 3.0
+        state = mesh_ops.fusion_state(n, self.density_plane[0].device)
+        n_views = 0
+        for depth, opacity, proj in fusion.slabs:
+            if depth.dim() != 3 or tuple(depth.shape[1:]) != (fusion.H, fusion.W):
+                raise ValueError("fusion: a slab's depth is [V, %d, %d] (got %s)" % (fusion.H, fusion.W, tuple(depth.shape)))
+            mesh_ops.fusion_integrate(state, depth, opacity, proj, lo, hi, trunc, min_opacity=fusion.min_opacity, carve=fusion.carve)
+            n_views += int(depth.shape[0])
+        vol, seen = mesh_ops.fusion_lattice(state, fusion.min_views)
+        return vol, seen, n_views
 
     @torch.no_grad()
     def updateAlphaMask(self, gridSize=(200, 200, 200)):
